@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: BN256 G1 MSM throughput through CommitmentKey::commit on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one MSM (the whole commit hot path: digit recoding, bucket sort, bucket accumulation,
 bucket reduction, window combine, to_affine) over one batch of synthetic scalars, with scalars and
@@ -94,7 +94,11 @@ def main():
                     help="REHEARSAL ONLY: all ranks share GPU 0 and exchange over gloo -- the whole multi-rank path with the product library on a one-GPU box; never a measurement")
     ap.add_argument("--emulate", action="store_true",
                     help="REHEARSAL ONLY: gloo + the test-only host emulation of the kernels, to exercise the multi-rank launch on a box without GPUs; never a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the commitment of the last step as DIR/msm_commitment.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -194,6 +198,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if (args.emulate or args.rehearse_one_gpu) else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = total / (elapsed / args.steps) / 1e6
@@ -286,6 +292,16 @@ def main():
     if rank == 0:
         real_stdout.write(json.dumps(out) + "\n")
         real_stdout.flush()
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, for comparing two builds output for
+    output (the synthetic inputs are seeded, so the same arguments give the same inputs).  The commit returns one affine
+    point, x || y as 4 little-endian u64 limbs each in Montgomery form; every limb is stored as its two 32-bit halves, low
+    first, which float64 holds exactly: (2, 8) float64, row 0 = x, row 1 = y."""
+    words = np.asarray(result, dtype=np.uint64).reshape(2, 4).astype("<u8").view("<u4")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_commitment.npy"), words.astype(np.float64))
 
 
 def multi_gpu_extras(lib, cm, dist, rank, n_gpus, total_log_n, args):

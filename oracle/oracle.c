@@ -4,7 +4,7 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this
  * library.  The product (mira_amd/, libmira_gpu.so) never links, loads or calls it.
  *
- * Restated here (paths relative to /root/reference):
+ * Restated here (paths relative to the reference repository, joshbeal/mira):
  *   - radix-2 NTT                src/fft.rs:12-27, 51-115, 118-155, 160-174, 178-226
  *   - CommitmentKey::commit      src/commitment.rs:78-87
  *   - best_multiexp              halo2_proofs::arithmetic (THIRD PARTY, source absent:

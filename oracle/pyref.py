@@ -5,7 +5,7 @@ module.  The product (mira_amd/) never does: it fails loudly when the HIP librar
 missing.
 
 What is restated, with the reference lines each function follows
-(paths relative to /root/reference):
+(paths relative to the reference repository, joshbeal/mira):
 
 * radix-2 NTT                 src/fft.rs:12-27 (omega derivation), :51-115 (best_fft),
                               :118-155 (recursive butterflies), :160-174 (fft/ifft),

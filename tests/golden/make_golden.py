@@ -25,7 +25,7 @@ def pt(p):
 def main():
     # ---- the reference's own vectors (data only) ------------------------------------------
     ref = {
-        "fft_simple_input_test": {  # /root/reference/src/fft.rs:238-257
+        "fft_simple_input_test": {  # src/fft.rs:238-257
             "source": "src/fft.rs:240-249", "log_n": 3, "input": list(range(8)),
             "output_decimal": [
                 "28",
@@ -36,12 +36,12 @@ def main():
                 "21819324486465344583084855339414673932756646216253763595445789781091758847675",
                 "21888242871839275204614721864072299718383108512864252727949815652902133356753",
                 "21819324486465344547821487577044723192426134441150200363949012713744408569955"]},
-        "fr_modulus_minus_one": {  # /root/reference/src/digest.rs:101-105
+        "fr_modulus_minus_one": {  # src/digest.rs:101-105
             "source": "src/digest.rs:103",
             "decimal": "21888242871839275222246405745257275088548364400416034343698204186575808495616"},
-        "g1_scalar_mul": {  # /root/reference/src/digest.rs:98-113: (r-1)*G == -G
+        "g1_scalar_mul": {  # src/digest.rs:98-113: (r-1)*G == -G
             "source": "src/digest.rs:98-113", "statement": "(r-1) * G1::generator() == -G1::generator()"},
-        "bn254_g2_generator": {  # /root/reference/src/gadgets/ecc2.rs:156-180
+        "bn254_g2_generator": {  # src/gadgets/ecc2.rs:156-180
             "source": "src/gadgets/ecc2.rs:159-176",
             "x": ["10857046999023057135944570762232829481370756359578518086990519993285655852781",
                   "11559732032986387107991004021392285783925812861821192530917403151452391805634"],
