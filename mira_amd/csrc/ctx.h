@@ -158,7 +158,7 @@ struct Bases {
     mutable uint32_t stat_hist[256] = {0};
     mutable size_t stat_n = 0;
     mutable int stat_kind = 0;     // what was histogrammed: 0 = whole scalars (per-window path, shared-bucket sets), 1 = the halves of the GLV split
-    // Width trials (capi.hip: trial_*): successive fold steps commit vectors of one shape over one key thousands of times, so the
+    // Width trials (msm_plan.hip: trial_*): successive fold steps commit vectors of one shape over one key thousands of times, so the
     // planner's choice for a shape is CHECKED against its neighbours on the first few commits -- the model's width and the four
     // around it, each timed twice -- and the fastest one measured is kept.  Never changes a result.
     struct WidthTrial {
@@ -242,31 +242,35 @@ static inline void plan_reduction(MsmPlan &p, uint32_t want_pieces) {
     p.nchunks = p.B >> p.lambda;
 }
 
-// per-curve translation units (msm_bn256.hip / msm_grumpkin.hip)
-// h_scalars != null: the scalars are still in host memory; d_scalars is then the device staging buffer they are copied to
-int msm_launch_bn256(const Bases &bs, size_t first, const void *d_scalars, const void *h_scalars, size_t n, const MsmPlan &p, uint64_t *host_windows);
-int msm_launch_grumpkin(const Bases &bs, size_t first, const void *d_scalars, const void *h_scalars, size_t n, const MsmPlan &p, uint64_t *host_windows);
-int msm_launch_table_bn256(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums);
-int msm_launch_table_grumpkin(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums);
-int build_tables_bn256(Bases &bs, uint32_t c, uint32_t W);
-int build_tables_grumpkin(Bases &bs, uint32_t c, uint32_t W);
-int build_glv_bn256(Bases &bs, const void *d_beta_r261);
-int build_glv_grumpkin(Bases &bs, const void *d_beta_r261);
-int curve_init_bn256();
-int convert_bases_bn256(const void *d_src, void *d_dst, size_t n);
-int convert_bases_grumpkin(const void *d_src, void *d_dst, size_t n);
-int curve_init_grumpkin();
-int synth_scalars_bn256(size_t n, uint64_t index0, uint64_t seed, int kind, void *d_out);
-int synth_scalars_grumpkin(size_t n, uint64_t index0, uint64_t seed, int kind, void *d_out);
-int synth_bases_bn256(size_t n, uint64_t index0, uint64_t seed, void *d_out);
-int synth_bases_grumpkin(size_t n, uint64_t index0, uint64_t seed, void *d_out);
-int check_bases_bn256(const Bases &bs, uint32_t *d_bad);
-int check_bases_grumpkin(const Bases &bs, uint32_t *d_bad);
-// key cache file <-> HBM (msm_host.cuh): read 2^k points in chunks beside their conversion / validation; write
-int load_bases_file_bn256(Bases &b, int fd, bool validate, uint32_t *d_bad);
-int load_bases_file_grumpkin(Bases &b, int fd, bool validate, uint32_t *d_bad);
-int save_bases_file_bn256(const Bases &b, int fd);
-int save_bases_file_grumpkin(const Bases &b, int fd);
+// The curve-specific operations, one table per curve (msm_host.cuh: make_curve_ops, instantiated once in each curve's translation
+// unit).  One indirect call per operation; everything below it is compiled for its curve.
+struct CurveOps {
+    int (*init)();
+    // h_scalars != null: the scalars are still in host memory; d_scalars is then the device staging buffer they are copied to
+    int (*msm_launch)(const Bases &bs, size_t first, const void *d_scalars, const void *h_scalars, size_t n, const MsmPlan &p, uint64_t *host_windows);
+    int (*msm_launch_table)(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums);
+    int (*build_tables)(Bases &bs, uint32_t c, uint32_t W);
+    int (*build_glv)(Bases &bs);
+    int (*convert_bases)(const void *d_src, void *d_dst, size_t n);
+    int (*check_bases)(const Bases &bs, uint32_t *d_bad);
+    int (*export_bases)(const Bases &bs, size_t first, size_t n, void *d_out);
+    int (*synth_scalars)(size_t n, uint64_t index0, uint64_t seed, int kind, void *d_out);
+    int (*synth_bases)(size_t n, uint64_t index0, uint64_t seed, void *d_out);
+    // key cache file <-> HBM: read 2^k points in chunks beside their conversion / validation; write
+    int (*load_bases_file)(Bases &b, int fd, bool validate, uint32_t *d_bad);
+    int (*save_bases_file)(const Bases &b, int fd);
+};
+extern const CurveOps CURVE_OPS_BN256, CURVE_OPS_GRUMPKIN;
+static inline const CurveOps &curve_ops(int curve) { return curve == MIRA_CURVE_BN256 ? CURVE_OPS_BN256 : CURVE_OPS_GRUMPKIN; }
+
+// The device constants block g.consts, written once by upload_consts (capi.hip); [curve] = MIRA_CURVE_*.
+struct DevConsts {
+    uint64_t gen[2][8];         // generator x, y (R form)                           bytes 0 / 64
+    uint64_t b_r261[2][4];      // curve constant b * 2^261 (R' form)                128 / 160
+    uint64_t beta_r261[2][4];   // beta * 2^261 of the endomorphism (glv.cuh)        192 / 224
+};
+static_assert(sizeof(DevConsts) == 256, "the layout above");
+static inline const DevConsts *dev_consts() { return reinterpret_cast<const DevConsts *>(g.consts.p); }
 
 // fold.hip
 int fold_witness_device(int field, void *d_out, const void *d_w1, const void *d_w2, const uint64_t r[4], size_t n);
@@ -276,8 +280,6 @@ int fold_relaxed_device(int field, void *d_w_out, const void *d_w1, const void *
 int lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint64_t *coeffs, size_t K, size_t n);
 int lincomb_multi_device(int field, void *const *d_outs, size_t M, const void *const *d_vecs, size_t J, const uint64_t *coeffs, size_t n);
 int pow_tree_reduce_device(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out);
-int export_bases_bn256(const Bases &bs, size_t first, size_t n, void *d_out);
-int export_bases_grumpkin(const Bases &bs, size_t first, size_t n, void *d_out);
 
 // graph.hip
 int graph_compile(int field, const mira_graph *gr, uint32_t num_challenges, uint32_t num_columns, uint64_t *handle_out);

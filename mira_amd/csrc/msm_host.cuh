@@ -339,14 +339,16 @@ template <class FS> static int synth_scalars(size_t n, uint64_t index0, uint64_t
     RT_CHECK(rt_sync(g.stream));
     return MIRA_OK;
 }
-template <class FB> static int synth_bases(size_t n, uint64_t index0, uint64_t seed, const unsigned char *d_gen, void *d_out) {
-    LAUNCH(k_synth_bases<FB>, ceil_div(n, 64), 64, 0, g.stream, (uint64_t)n, index0, seed, d_gen, reinterpret_cast<unsigned char *>(d_out));
+template <class FB, int CURVE> static int synth_bases(size_t n, uint64_t index0, uint64_t seed, void *d_out) {
+    LAUNCH(k_synth_bases<FB>, ceil_div(n, 64), 64, 0, g.stream, (uint64_t)n, index0, seed, reinterpret_cast<const unsigned char *>(dev_consts()->gen[CURVE]),
+           reinterpret_cast<unsigned char *>(d_out));
     RT_CHECK(rt_last());
     RT_CHECK(rt_sync(g.stream));
     return MIRA_OK;
 }
-template <class F> static int check_bases(const Bases &bs, const unsigned char *d_b, uint32_t *d_bad) {
-    LAUNCH(k_check_on_curve<F>, ceil_div(bs.n, 256), 256, 0, g.stream, (const unsigned char *)bs.d, (uint64_t)bs.n, d_b, d_bad);
+template <class F, int CURVE> static int check_bases(const Bases &bs, uint32_t *d_bad) {
+    LAUNCH(k_check_on_curve<F>, ceil_div(bs.n, 256), 256, 0, g.stream, (const unsigned char *)bs.d, (uint64_t)bs.n,
+           reinterpret_cast<const unsigned char *>(dev_consts()->b_r261[CURVE]), d_bad);
     RT_CHECK(rt_last());
     return MIRA_OK;
 }
@@ -368,7 +370,7 @@ template <class F> static int export_bases(const Bases &bs, size_t first, size_t
 }
 
 // ---- the interleaved key of the GLV split (glv.cuh) -----------------------------------------------
-template <class F> static int build_glv(Bases &bs, const void *d_beta_r261) {
+template <class F, int CURVE> static int build_glv(Bases &bs) {
     const size_t bytes = (size_t)bs.n * 128;
     void *t = nullptr;
     if (rt_malloc(&t, bytes) != hipSuccess || !t) {
@@ -376,7 +378,7 @@ template <class F> static int build_glv(Bases &bs, const void *d_beta_r261) {
         return MIRA_E_ALLOC;
     }
     LAUNCH(k_glv_bases<F>, ceil_div(bs.n, 256), 256, 0, g.stream, reinterpret_cast<const unsigned char *>(bs.d), reinterpret_cast<unsigned char *>(t), (uint64_t)bs.n,
-           reinterpret_cast<const unsigned char *>(d_beta_r261));
+           reinterpret_cast<const unsigned char *>(dev_consts()->beta_r261[CURVE]));
     if (rt_last() != hipSuccess || rt_sync(g.stream) != hipSuccess) { (void)rt_free(t); set_error("building the endomorphism copy of the key failed"); return MIRA_E_NO_DEVICE; }
     bs.glv = t;
     return MIRA_OK;
@@ -529,7 +531,8 @@ static inline int read_exact_parallel(int fd, unsigned char *dst, size_t bytes, 
     for (int f : fail) if (f) return 1;
     return 0;
 }
-template <class F> static int load_bases_file(Bases &b, int fd, bool validate, const unsigned char *d_curve_b, uint32_t *d_bad) {
+template <class F, int CURVE> static int load_bases_file(Bases &b, int fd, bool validate, uint32_t *d_bad) {
+    const unsigned char *d_curve_b = reinterpret_cast<const unsigned char *>(dev_consts()->b_r261[CURVE]);
     unsigned char *pinned[2] = {nullptr, nullptr};
     const size_t chunk_bytes = std::min(b.n, KEYFILE_CHUNK_POINTS) * 64;
     auto body = [&]() -> int {
@@ -594,3 +597,9 @@ template <class F> static int save_bases_file(const Bases &b, int fd) {
     return rc;
 }
 
+// The operations of one curve: F29 its coordinates on the device, FB on the host, FS its scalars; CURVE = MIRA_CURVE_*.  (No two
+// members of CurveOps share a signature: the compiler checks this order.)
+template <class F29, class FB, class FS, int CURVE> static CurveOps make_curve_ops() {
+    return {curve_init<F29, FS>, msm_launch<F29, FS>, msm_launch_table<F29, FS>, build_tables<F29>, build_glv<F29, CURVE>, convert_bases<F29>,
+            check_bases<F29, CURVE>, export_bases<F29>, synth_scalars<FS>, synth_bases<FB, CURVE>, load_bases_file<F29, CURVE>, save_bases_file<F29>};
+}

@@ -16,7 +16,7 @@
 // the tree for 2^kappa chunks per workgroup in LDS; k_set_finish (one workgroup per set) runs the remaining levels over
 // the workgroups' nodes and leaves the set's result as P PIECES
 //     piece_p = sum_(pos in [s_p, s_(p+1))) 2^(pos - s_p) X_pos,    X_0 = V,  X_(lambda + t) = D_t,
-// so that T = sum_p 2^(s_p) piece_p: the host's chain of doublings over the windows (capi.hip: horner_pieces) stops at
+// so that T = sum_p 2^(s_p) piece_p: the host's chain of doublings over the windows (host_curve.hpp: horner_pieces) stops at
 // every piece instead of every window -- the doublings it does anyway, P - 1 more additions per window -- and the
 // device's own Horner chains are (cb / P) long instead of cb.  P = 1 gives the plain window sum (sharded partials).
 //

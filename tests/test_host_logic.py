@@ -273,7 +273,7 @@ def test_width_trials_settle_and_never_change_the_point(emu_lib):
 
 
 def test_planner_tables_are_sane(emu_lib):
-    """The window width comes from measured wall-time tables (capi.hip: plan_wall_us, glv_wall_us, shared_wall_us) that go stale
+    """The window width comes from measured wall-time tables (msm_plan.hip: PLAN_WALLS, GLV_WALLS, SHARED_WALLS) that go stale
     whenever a tail kernel changes (round 4: the mid-round table cost planned 2^17-pair commits 17 %).  This cannot re-measure them;
     it pins what every calibration so far agrees on, so that a mis-typed row shows: widths never shrink as commits grow from 2^18 pairs
     (12 and 13 bits tie below), the fold step's 2^16 .. 2^18-pair commits take 12 or 13 bits, and everything from 2^21 pairs takes the

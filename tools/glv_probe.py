@@ -23,7 +23,7 @@ def plan():
 
 
 def calibrate():
-    """rows of glv_wall_us (capi.hip): wall time in microseconds of one GLV commit of 2^k uniform pairs under every width"""
+    """rows of GLV_WALLS (msm_plan.hip): wall time in microseconds of one GLV commit of 2^k uniform pairs under every width"""
     sizes = [10, 12, 14, 15, 16, 17, 18, 19, 20, 21, 22]
     print("static const int glv_log_n[%d] = {%s};" % (len(sizes), ", ".join(map(str, sizes))))
     for k in sizes:

@@ -1,10 +1,10 @@
 """Development probe: wall time of one commit for every window width, across the sizes the planner
-(plan_cost_us in capi.hip) has to decide for.  Output feeds its base_us table and candidate list."""
+(plan_cost_us in msm_plan.hip) has to decide for.  Output feeds its base_us table and candidate list."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mira_amd import _lib, commitment as cm
 lib = _lib.load()
-if os.environ.get("PLAIN"):                    # the per-window path alone (the rows of plan_wall_us): no endomorphism copy is built or used
+if os.environ.get("PLAIN"):                    # the per-window path alone (the rows of PLAN_WALLS): no endomorphism copy is built or used
     lib.tune(_lib.TUNE_GLV_AUTO_MAX_LOG, 0)
     lib.tune(_lib.TUNE_GLV, 0)
 cases = [(64, 0), (1024, 0), (8192, 0), (32768, 0), (65536, 0), (131072, 0), (1 << 18, 0), (1 << 19, 0), (1 << 20, 0), (1 << 21, 0), (14 << 17, 1), (7 << 17, 1), (131072, 1)]

@@ -1,6 +1,6 @@
 """Development probe: wall time of one commit over the shared-bucket table set of every width 8 .. 16
 (mira_msm_precompute_ex, MIRA_TUNE_TABLE_WIDTH), beside the per-window path, across the sizes a fold
-step commits.  Output feeds shared_wall_us in capi.hip.  With `stages` as first argument it also prints
+step commits.  Output feeds SHARED_WALLS in msm_plan.hip.  With `stages` as first argument it also prints
 the stage timings of every width at 131 072 pairs."""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
