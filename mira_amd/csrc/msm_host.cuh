@@ -113,7 +113,7 @@ static int msm_launch_body(const Bases &bs, size_t first, const void *d_scalars,
     const uint32_t scan_blocks = ceil_div(p.NB, SCAN_TILE);
     if (scan_blocks > 1024) { set_error("window configuration exceeds the scan capacity"); return MIRA_E_UNSUPPORTED; }
     if ((rc = g.block_sums.ensure(1024 * 4))) return rc;
-    if ((rc = g.sorted_idx.ensure(entries_max * 4 + 8))) return rc;
+    if ((rc = g.sorted_idx.ensure(entries_max * 4 + 8 + ACC_STAGE_PAD))) return rc;
     const size_t staged_min_n = tuned(MIRA_TUNE_STAGED_MIN_N, (size_t)1 << 19);
     if (nmax * p.count >= staged_min_n && p.c >= 9) {
         if ((rc = g.part.ensure(entries_max * 8 + 8))) return rc;
@@ -238,12 +238,12 @@ static int msm_launch_body(const Bases &bs, size_t first, const void *d_scalars,
                        (uint32_t)nc, p.B, tile, reinterpret_cast<uint32_t *>(g.cursor.p), reinterpret_cast<uint32_t *>(g.sorted_idx.p), wgroup, idx_stride, idx_first);
         tm_mark("scatter");
         if (add)
-            LAUNCH((k_accumulate<F, true>), ceil_div(p.T, 128), 128, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
+            LAUNCH((k_accumulate<F, true>), ceil_div(p.T, ACC_BLOCK), ACC_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
                    reinterpret_cast<const uint32_t *>(g.offsets.p), p.NB, bases, (const uint32_t *)plan,
                    reinterpret_cast<unsigned char *>(g.bucket_sums.p), reinterpret_cast<unsigned char *>(g.head_part.p),
                    reinterpret_cast<unsigned char *>(g.tail_part.p), reinterpret_cast<uint32_t *>(g.tail_key.p), heavy_count, heavy_runs, heavy_subs, heavy_meds);
         else
-            LAUNCH((k_accumulate<F, false>), ceil_div(p.T, 128), 128, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
+            LAUNCH((k_accumulate<F, false>), ceil_div(p.T, ACC_BLOCK), ACC_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
                    reinterpret_cast<const uint32_t *>(g.offsets.p), p.NB, bases, (const uint32_t *)plan,
                    reinterpret_cast<unsigned char *>(g.bucket_sums.p), reinterpret_cast<unsigned char *>(g.head_part.p),
                    reinterpret_cast<unsigned char *>(g.tail_part.p), reinterpret_cast<uint32_t *>(g.tail_key.p), heavy_count, heavy_runs, heavy_subs, heavy_meds);
@@ -421,7 +421,7 @@ static int msm_launch_table(const Bases &bs, size_t first, const void *d_scalars
     if ((rc = g.cursor.ensure(((size_t)TABLE_CB + 1) * 4))) return rc;
     if ((rc = g.block_sums.ensure(1024 * 4))) return rc;
     if ((rc = g.part.ensure(entries * 8 + 8))) return rc;
-    if ((rc = g.sorted_idx.ensure(entries * 4 + 8))) return rc;
+    if ((rc = g.sorted_idx.ensure(entries * 4 + 8 + ACC_STAGE_PAD))) return rc;
     if ((rc = g.offsets.ensure(((size_t)TABLE_B + 1) * 4))) return rc;
     if ((rc = g.fine_counts.ensure(((size_t)TABLE_B + 1) * 4))) return rc;
     if ((rc = g.fine_cursor.ensure(((size_t)TABLE_B + 1) * 4))) return rc;
@@ -478,7 +478,7 @@ static int msm_launch_table(const Bases &bs, size_t first, const void *d_scalars
     LAUNCH_BARRIER((k_stage2<STAGE_TILE, STAGE_MAX_KEYS2>), ceil_div(entries, STAGE_TILE), 1024, (size_t)STAGE_TILE * 6, st, reinterpret_cast<const U2 *>(g.part.p), coarse_total,
                         TABLE_FINE_BITS, reinterpret_cast<uint32_t *>(g.fine_cursor.p), reinterpret_cast<uint32_t *>(g.sorted_idx.p));
     tm_mark("sort_level2");
-    LAUNCH((k_accumulate<F, false>), ceil_div(T, 128), 128, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
+    LAUNCH((k_accumulate<F, false>), ceil_div(T, ACC_BLOCK), ACC_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
            reinterpret_cast<const uint32_t *>(g.offsets.p), TABLE_B, reinterpret_cast<const unsigned char *>(bs.tables), (const uint32_t *)plan,
            reinterpret_cast<unsigned char *>(g.bucket_sums.p), reinterpret_cast<unsigned char *>(g.head_part.p),
            reinterpret_cast<unsigned char *>(g.tail_part.p), reinterpret_cast<uint32_t *>(g.tail_key.p), heavy_count, heavy_runs, heavy_subs, heavy_meds);

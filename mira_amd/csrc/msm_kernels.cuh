@@ -389,12 +389,54 @@ template <bool ADD, class F> DEV Xyzz29<F> run_start(const unsigned char *bucket
 #ifdef MSM_PROBE_STAMPS
 static __device__ uint64_t g_acc_stamps[4096 * 3];
 #endif
+// Staged entry stream of k_accumulate.  A lane reads its sorted entries from LDS: blocks of ACC_STAGE entries, 16-byte aligned in
+// `sorted`, copied by four global_load_lds_dwordx4 (no VGPRs held while they are in flight), two blocks per lane (the next one is
+// requested when the first entry of the current one is read, ~ACC_STAGE iterations before it is needed).  In LDS a wave's block
+// is four slices of 64 lanes x 16 bytes, the order in which the hardware writes them.  A block may reach up to ACC_STAGE - 1
+// entries past the end of the sorted entries: the buffer carries ACC_STAGE_PAD bytes behind them (msm_host.cuh).
+// (-DMSM_ACC_STAGE=0: the per-iteration 4-byte global load of round 4, for same-box A/B builds.)
+#ifndef MSM_ACC_STAGE
+#define MSM_ACC_STAGE 1
+#endif
+static constexpr uint32_t ACC_BLOCK = 128, ACC_STAGE = 16, ACC_STAGE_PAD = ACC_STAGE * 4;
+static constexpr uint32_t ACC_STAGE_WAVE_WORDS = 2 * 64 * ACC_STAGE;        // two blocks of a wave: 8 KiB
+DEV uint32_t acc_lane() { return threadIdx.x & 63u; }
+#ifdef MIRA_CPU_EMU
+DEV uint32_t acc_wave() { return threadIdx.x >> 6; }
+#else
+DEV uint32_t acc_wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+#endif
+// the lane's entries src[0 .. ACC_STAGE) -> block `buf` of its wave's stage (buf is the same in every lane that calls this at once)
+DEV void acc_stage_block(uint32_t *wave_stage, uint32_t buf, const uint32_t *src) {
+#ifdef MIRA_CPU_EMU
+    for (uint32_t q = 0; q < ACC_STAGE / 4; q++) memcpy(wave_stage + buf * (64 * ACC_STAGE) + q * 256 + acc_lane() * 4, src + 4 * q, 16);
+#else
+    uint32_t *dst = wave_stage + __builtin_amdgcn_readfirstlane(buf) * (64 * ACC_STAGE);
+#pragma unroll
+    for (uint32_t q = 0; q < ACC_STAGE / 4; q++)
+        __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)(src + 4 * q),
+                                         (__attribute__((address_space(3))) void *)(dst + q * 256), 16, 0, 0);
+#endif
+}
+// entry r of the lane's staged stream (r counted from the 16-byte aligned start of its first block)
+DEV uint32_t acc_staged(const uint32_t *wave_stage, uint32_t r) {
+    return wave_stage[((r / ACC_STAGE) & 1u) * (64 * ACC_STAGE) + ((r % ACC_STAGE) >> 2) * 256 + acc_lane() * 4 + (r & 3u)];
+}
+// every LDS write of the stage requested so far has landed (the loads write LDS behind the compiler's back: it does not wait for them)
+DEV void acc_stage_wait() {
+#ifndef MIRA_CPU_EMU
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                        // vmcnt(0) (gfx9 encoding)
+#endif
+}
 template <class F, bool ADD>
-KERNEL void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_accumulate(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ offsets, uint32_t NB,
+KERNEL void __launch_bounds__(ACC_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 3))) k_accumulate(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ offsets, uint32_t NB,
                          const unsigned char *__restrict__ bases,
                          const uint32_t *__restrict__ plan, unsigned char *__restrict__ bucket_sums,
                          unsigned char *__restrict__ head_part, unsigned char *__restrict__ tail_part, uint32_t *__restrict__ tail_key,
                          uint32_t *__restrict__ heavy_ctr, U4 *__restrict__ runs, U4 *__restrict__ subs, U4 *__restrict__ meds) {
+#if MSM_ACC_STAGE
+    __shared__ __attribute__((aligned(16))) uint32_t stage[(ACC_BLOCK / 64) * ACC_STAGE_WAVE_WORDS];   // 16 KiB per workgroup
+#endif
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 #ifdef MSM_PROBE_STAMPS
     const uint64_t probe_t0 = __builtin_amdgcn_s_memrealtime();
@@ -421,9 +463,18 @@ KERNEL void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_
     // the current mixed add (about 9k issue cycles per wave) runs
     uint32_t ent0 = sorted[start];
     uint32_t ent1 = (start + 1 < end) ? sorted[start + 1] : ent0;
+#if MSM_ACC_STAGE
+    uint32_t *wave_stage = stage + acc_wave() * ACC_STAGE_WAVE_WORDS;
+    const uint32_t stage_at = start & ~3u;                   // staged blocks begin 16-byte aligned
+    acc_stage_block(wave_stage, 0, sorted + stage_at);
+    if (stage_at + ACC_STAGE < end) acc_stage_block(wave_stage, 1, sorted + stage_at + ACC_STAGE);
+#endif
     const U4 *bp = reinterpret_cast<const U4 *>(bases + (size_t)(ent0 & 0x7FFFFFFFu) * 64);
     U4 r0 = bp[0], r1 = bp[1], r2 = bp[2], r3 = bp[3];
     for (uint32_t j = start; j < end; j++) {
+#if MSM_ACC_STAGE
+        acc_stage_wait();                                    // free: the base loads of the last iteration were waited for anyway
+#endif
         const uint32_t e = ent0;
         const U4 c0 = r0, c1 = r1, c2 = r2, c3 = r3;
         // Unconditional loads (ent1 and the clamped index are always valid; the last iterations fetch a
@@ -433,7 +484,18 @@ KERNEL void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_
         bp = reinterpret_cast<const U4 *>(bases + (size_t)(ent1 & 0x7FFFFFFFu) * 64);
         r0 = bp[0]; r1 = bp[1]; r2 = bp[2]; r3 = bp[3];
         ent0 = ent1;
+#if MSM_ACC_STAGE
+        {
+            const uint32_t r = ((j + 2 < end) ? j + 2 : end - 1) - stage_at;
+            ent1 = acc_staged(wave_stage, r);
+            // the first entry of a block is read: the block after it goes to the other buffer, whose entries are all read
+            // (issued behind the read, so that the compiler's ordering of the LDS accesses costs no wait)
+            if (r % ACC_STAGE == 0 && stage_at + r + ACC_STAGE < end)
+                acc_stage_block(wave_stage, (r / ACC_STAGE + 1) & 1u, sorted + stage_at + r + ACC_STAGE);
+        }
+#else
         ent1 = sorted[(j + 2 < end) ? j + 2 : end - 1];
+#endif
         if (j == run_end) {                                  // the run of `cur` is complete
             if (first && cont_prev) xyzz29_store(head_part + (size_t)t * XYZZ29_BYTES, acc);
             else xyzz29_store(bucket_sums + (size_t)cur * XYZZ29_BYTES, acc);

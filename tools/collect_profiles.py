@@ -81,3 +81,38 @@ if ntt:
     print("ntt 2^24 traffic GB:", traffic["ntt_2p24"] / 1e9)
 if traffic:
     json.dump(traffic, open("profiles/pmc_traffic.json", "w"), indent=1)
+
+# ---- k_accumulate against the previous profile: a slower kernel must not pass as a slower box ------------------
+# GRBM_GUI_ACTIVE, SQ_WAIT_ANY (cycles) and FETCH_SIZE (bytes) do not depend on the clock; more than LIMIT apart from
+# the last committed profile and this exits non-zero, to be explained before the profile is kept.
+LIMIT = 0.015
+
+
+def acc_counters(t):
+    vals = {}
+    p = f"profiles/{t}_msm2p22_pmc_valu.txt"
+    if os.path.exists(p):
+        for line in open(p):
+            f = line.split()
+            if len(f) == 5 and f[0] in ("GRBM_GUI_ACTIVE", "SQ_WAIT_ANY") and f[1] == "launches" and f[3] == "avg":
+                vals[f[0]] = float(f[-1])
+    p = f"profiles/{t}_msm2p22_pmc_fetch_write.csv"
+    if os.path.exists(p):
+        for r in csv.DictReader(open(p)):
+            if "k_accumulate" in r["kernel"] and r["counter"] == "FETCH_SIZE":
+                vals["FETCH_SIZE"] = float(r["avg_value_KB"])
+    return vals
+
+
+now = acc_counters(ftag)
+prev_tags = sorted({os.path.basename(p).split("_msm2p22_pmc_")[0] for p in glob.glob("profiles/*_msm2p22_pmc_*")} - {ftag})
+prev_tags = [t for t in prev_tags if t < ftag and acc_counters(t)]
+if now and prev_tags:
+    prev, drift = acc_counters(prev_tags[-1]), []
+    for c, v in sorted(now.items()):
+        if c in prev and abs(v / prev[c] - 1) > LIMIT:
+            drift.append(f"{c} {prev[c]:.0f} -> {v:.0f} ({(v / prev[c] - 1) * 100:+.1f} %)")
+    if drift:
+        print(f"k_accumulate differs from profiles/{prev_tags[-1]}_*: " + "; ".join(drift))
+        sys.exit(1)
+    print(f"k_accumulate within {LIMIT * 100:.1f} % of profiles/{prev_tags[-1]}_*")
