@@ -1,4 +1,4 @@
-// Specialised cross-term kernels: the compiled instruction stream of one graph (graph.hip) written out as
+// Specialised cross-term kernels: the compiled instruction stream of one graph (graph_stream.h) written out as
 // straight-line HIP and compiled for gfx950 at run time (hiprtc).
 //
 // k_graph_eval (graph_kernels.cuh) INTERPRETS the stream: every instruction is decoded with wave-uniform branches,
@@ -14,13 +14,13 @@
 //
 // hiprtc is loaded with dlopen at first use: a machine without it keeps the interpreter (mira_graph_specialize
 // reports MIRA_E_JIT_UNAVAILABLE).  The headers the source includes (field29.cuh, field.cuh, platform.h) are part of
-// the library: the build embeds their text (Makefile: jit_headers.inc) and hands it to hiprtc as named headers, so
-// nothing has to lie beside libmira_gpu.so.
+// the library: the build embeds their text (Makefile: jit_headers.inc) and graph_jit.hip hands it to hiprtc as named
+// headers, so nothing has to lie beside libmira_gpu.so.
 #pragma once
 #include <string>
 #include <vector>
 
-#include "graph_kernels.cuh"
+#include "graph_stream.h"
 
 namespace graphjit {
 
@@ -28,11 +28,9 @@ constexpr uint32_t MAX_INSTR = 1536;            // longer streams stay with the 
 constexpr size_t LOADS_AHEAD_DEFAULT = 4;       // column reads in flight ahead of their use (MIRA_TUNE_JIT_LOADS_AHEAD)
 constexpr uint32_t BLOCK = 64;                  // lanes per workgroup of a specialised kernel (measured: 64 ahead of 128 and 256 by 3 - 6 %)
 
-inline uint32_t words_of(uint32_t head) { const uint32_t op = head & 0xFFu; return op == GOP_MAC ? 7u : (op == GOP_ADD || op == GOP_SUB || op == GOP_MUL) ? 5u : 4u; }
-
 // HIP source of one program.  `rotations`: the graph's rotation table (baked in: a rotation of zero reads the lane's own row).
 // `kinds`: MIRA_COL_FIELD / MIRA_COL_BOOL of every column index the stream reads (others: anything).
-inline std::string source(int field, const std::vector<uint32_t> &stream, uint32_t ninstr, const std::vector<int32_t> &rotations, const std::vector<uint32_t> &kinds,
+inline std::string source(int field, const std::vector<uint32_t> &stream, const std::vector<int32_t> &rotations, const std::vector<uint32_t> &kinds,
                           size_t loads_ahead = LOADS_AHEAD_DEFAULT) {
     std::string s;
     s.reserve(64 * 1024);
@@ -59,41 +57,22 @@ inline std::string source(int field, const std::vector<uint32_t> &stream, uint32
          "              unsigned char *__restrict__ out, uint64_t nrows) {\n"
          "    const uint64_t T = (uint64_t)gridDim.x * blockDim.x;\n"
          "    for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; row < nrows; row += T) {\n";
-    // rows of the rotations the stream uses, once per row (rem_euclid, graph_evaluator.rs:51-53)
-    std::vector<char> rot_used(rotations.size(), 0);
-    {
-        size_t pos = 0;
-        for (uint32_t i = 0; i < ninstr; i++) {
-            const uint32_t head = stream[pos], op = head & 0xFFu;
-            const uint32_t nsrc = op == GOP_MAC ? 3u : (op == GOP_ADD || op == GOP_SUB || op == GOP_MUL) ? 2u : 1u;
-            for (uint32_t k = 0; k < nsrc; k++) {
-                const uint32_t w = stream[pos + 3 + k];
-                if ((w >> 29) == MIRA_SRC_COLUMN) rot_used[(w & 0x1FFFFFFFu) >> 20] = 1;
-            }
-            pos += words_of(head);
-        }
-    }
-    for (size_t r = 0; r < rotations.size(); r++) {
-        if (!rot_used[r] || rotations[r] == 0) continue;
-        s += "        uint64_t row_r" + std::to_string(r) + ";\n"
-             "        { int64_t rr = ((int64_t)row + (" + std::to_string(rotations[r]) + ")) % (int64_t)nrows; if (rr < 0) rr += (int64_t)nrows; row_r" + std::to_string(r) + " = (uint64_t)rr; }\n";
-    }
     // Column reads, in the order the stream consumes them.  Two waves per SIMD do not hide a load that is waited for where
     // it is issued (and the scheduling barriers keep the compiler from hoisting it), so the generator does the software
     // pipelining: the packed value of read k + LOADS_AHEAD is requested where read k is consumed, and unpacked at its use.
     struct ColRead { uint32_t col, rot; };
     std::vector<ColRead> reads;
-    {
-        size_t pos = 0;
-        for (uint32_t i = 0; i < ninstr; i++) {
-            const uint32_t head = stream[pos], op = head & 0xFFu;
-            const uint32_t nsrc = op == GOP_MAC ? 3u : (op == GOP_ADD || op == GOP_SUB || op == GOP_MUL) ? 2u : 1u;
-            for (uint32_t k = 0; k < nsrc; k++) {
-                const uint32_t w = stream[pos + 3 + k];
-                if ((w >> 29) == MIRA_SRC_COLUMN) reads.push_back({(w & 0x1FFFFFFFu) & 0xFFFFFu, (w & 0x1FFFFFFFu) >> 20});
-            }
-            pos += words_of(head);
-        }
+    for_each_instruction(stream.data(), stream.size(), [&](const uint32_t *ins) {
+        for (uint32_t k = 0; k < gop_operands(gop_op(ins[0])); k++)
+            if (src_kind(ins[3 + k]) == MIRA_SRC_COLUMN) reads.push_back({col_index(src_payload(ins[3 + k])), col_rotation(src_payload(ins[3 + k]))});
+    });
+    // rows of the rotations the stream uses, once per row (rem_euclid, graph_evaluator.rs:51-53)
+    std::vector<char> rot_used(rotations.size(), 0);
+    for (const ColRead &r : reads) rot_used[r.rot] = 1;
+    for (size_t r = 0; r < rotations.size(); r++) {
+        if (!rot_used[r] || rotations[r] == 0) continue;
+        s += "        uint64_t row_r" + std::to_string(r) + ";\n"
+             "        { int64_t rr = ((int64_t)row + (" + std::to_string(rotations[r]) + ")) % (int64_t)nrows; if (rr < 0) rr += (int64_t)nrows; row_r" + std::to_string(r) + " = (uint64_t)rr; }\n";
     }
     const size_t LOADS_AHEAD = loads_ahead;
     size_t issued = 0, consumed = 0;
@@ -109,22 +88,22 @@ inline std::string source(int field, const std::vector<uint32_t> &stream, uint32
     issue_until(LOADS_AHEAD);
     std::vector<std::string> slot_val;
     auto operand = [&](uint32_t w, uint32_t i) -> std::string {
-        const uint32_t kind = w >> 29, payload = w & 0x1FFFFFFFu;
+        const uint32_t kind = src_kind(w), payload = src_payload(w);
         if (kind == GRAPH_SRC_PREV) return "t" + std::to_string(i - 1);
         if (kind == MIRA_SRC_CONSTANT) return "jit_const(consts29, " + std::to_string(payload) + "u)";
         if (kind == MIRA_SRC_CHALLENGE) return "jit_const(chal29, " + std::to_string(payload) + "u)";
         if (kind == MIRA_SRC_INTERMEDIATE) return payload < slot_val.size() && !slot_val[payload].empty() ? slot_val[payload] : std::string("f29_zero<F>()");
         const size_t k = consumed++;                          // operands are resolved in stream order: this is read k
         issue_until(k + 1 + LOADS_AHEAD);
-        return is_bool(payload & 0xFFFFFu) ? "jit_bool(c" + std::to_string(k) + ")" : "f29_unpack_canonical<F>(c" + std::to_string(k) + ")";
+        return is_bool(col_index(payload)) ? "jit_bool(c" + std::to_string(k) + ")" : "f29_unpack_canonical<F>(c" + std::to_string(k) + ")";
     };
     auto bias = [](uint32_t K) { return K == 2 ? "2" : K == 4 ? "4" : K == 8 ? "8" : "16"; };   // graph_sub's cases
-    size_t pos = 0;
-    for (uint32_t i = 0; i < ninstr; i++) {
-        const uint32_t head = stream[pos], dst = stream[pos + 1], op = head & 0xFFu, K = head >> 8;
-        const uint32_t nsrc = op == GOP_MAC ? 3u : (op == GOP_ADD || op == GOP_SUB || op == GOP_MUL) ? 2u : 1u;
-        const std::string a = operand(stream[pos + 3], i), b = nsrc > 1 ? operand(stream[pos + 4], i) : std::string(), c3 = nsrc > 2 ? operand(stream[pos + 5], i) : std::string();
-        const std::string t = "t" + std::to_string(i);
+    uint32_t i = 0;
+    for_each_instruction(stream.data(), stream.size(), [&](const uint32_t *ins) {
+        const uint32_t op = gop_op(ins[0]), K = gop_bias(ins[0]), dst = ins[1];
+        std::string o[3];                                         // a, b, c: resolved in stream order
+        for (uint32_t k = 0; k < gop_operands(op); k++) o[k] = operand(ins[3 + k], i);
+        const std::string &a = o[0], &b = o[1], &c3 = o[2], t = "t" + std::to_string(i);
         std::string e;
         bool product = false;
         switch (op) {
@@ -146,9 +125,9 @@ inline std::string source(int field, const std::vector<uint32_t> &stream, uint32
             if (dst >= slot_val.size()) slot_val.resize(dst + 1);
             slot_val[dst] = t;
         }
-        pos += words_of(head);
-    }
-    s += "        fe_store(out + row * 32, reduce_once(f29_pack(t" + std::to_string(ninstr - 1) + ")));\n"
+        i++;
+    });
+    s += "        fe_store(out + row * 32, reduce_once(f29_pack(t" + std::to_string(i - 1) + ")));\n"
          "    }\n"
          "}\n";
     return s;
@@ -166,11 +145,14 @@ struct Rtc {
     int (*code)(void *, char *) = nullptr;
     int (*destroy)(void **) = nullptr;
     std::string error;
-    bool tried = false;
 };
-Rtc &rtc();                                                      // graph.hip
-// source -> code object; empty on failure (message in `err`).  Thread-safe once rtc() is loaded.
+// ---- graph_jit.hip ----
+Rtc &rtc();                                                      // loaded at the first call; `error` says why not
+// source -> code object; empty on failure (message in `err`).  Thread-safe.
 std::vector<char> compile(const std::string &src, std::string &err);
+// the code object an earlier process stored for this source (mira_graph_set_cache_dir), or empty
+std::vector<char> cache_load(const std::string &src);
+void cache_store(const std::string &src, const std::vector<char> &code);   // best effort
 #endif
 
 }   // namespace graphjit

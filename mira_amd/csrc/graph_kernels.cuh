@@ -7,38 +7,26 @@
 // reads are 32-byte loads at consecutive rows (rotations shift the whole wave), and the
 // intermediates live in a slot-major workspace ws[slot][limb][lane] so that every intermediate
 // access is nine fully coalesced dword bursts per wave.  Slots are the host's register allocation of
-// the intermediates (graph.hip): a handful, reused, so the workspace stays cache resident.
+// the intermediates (graph_compile.hip): a handful, reused, so the workspace stays cache resident.
 //
 // Arithmetic: 9 x 29-bit limbs (field29.cuh: half the instructions of the 8 x 32-bit CIOS per
 // multiplication).  Values are "loose" between calculations; the host COMPILES the program
-// (graph.hip) with a proven bound for every value -- invariant: whatever is stored or forwarded is
+// (graph_compile.hip, the stream format in graph_stream.h) with a proven bound for every value -- invariant: whatever is stored or forwarded is
 // < 12 P, so any two values may be multiplied (144 <= 168) -- and inserts a normalising
 // multiplication by one where a chain of additions would leave the budget.  Columns are read as they lie
 // in memory (x * 2^256, no lifting product): the compiler tracks for every value the power of two it
-// carries (its "form", graph.hip), hands constants and challenges over in the form each use wants,
+// carries (its "form", graph_compile.h), hands constants and challenges over in the form each use wants,
 // and converts where forms cannot be made to agree; the program's last instruction leaves the result
 // as x * 2^256 below 2 P and the kernel stores it canonical.  Field results are exact, so every value
 // equals the reference's bit for bit whatever the order of rows.
 #pragma once
 #include "field29.cuh"
-#include "../../include/mira_gpu.h"
+#include "graph_stream.h"
 
 struct GraphCol {
     const unsigned char *p;
     uint32_t kind, pad;
 };
-
-// Compiled instruction stream: per instruction
-//   [op | K << 8]  [dst slot]  [bounds of a and b in 1/256 P: lo 16 | hi 16 bits]  [source a]  ([source b])
-// and for GOP_MAC (a * b + c: an addition that absorbed the product feeding it, graph.hip) two more: [source c] [bound of c]
-// INTERMEDIATE payloads are slots; GRAPH_SRC_PREV = the value of the instruction just before
-// (still in registers -- most results of a post-order expression walk are consumed by the very next
-// instruction and never touch the workspace).  K = the multiple of P a subtraction adds.  The
-// bounds word only feeds the test build's bound bookkeeping (F29_TRACK).
-static constexpr uint32_t GRAPH_SRC_PREV = 4u;
-static constexpr uint32_t GRAPH_NO_SLOT = 0xFFFFFFFFu;
-static constexpr uint32_t GOP_ADD = 0, GOP_SUB = 1, GOP_MUL = 2, GOP_SQR = 3, GOP_DBL = 4, GOP_NEG = 5, GOP_COPY = 6, GOP_NORM = 7, GOP_MAC = 8;
-static constexpr double GRAPH_MAX_BOUND = 12.0;          // of every stored or forwarded value, in multiples of P
 
 template <class F> DEV Fe29<F> graph_sub(const Fe29<F> &a, const Fe29<F> &b, uint32_t K) {
     switch (K) {                                         // smallest multiple of P above the subtrahend (chosen by the host)
@@ -76,7 +64,7 @@ KERNEL void __launch_bounds__(256) k_graph_eval(const GraphJob *__restrict__ job
     for (uint64_t row = lane; row < nrows; row += T) {
         Fe29<F> v = f29_zero<F>(), prev;
         auto fetch = [&](uint32_t s, uint32_t bound) -> Fe29<F> {
-            const uint32_t kind = s >> 29, payload = s & 0x1FFFFFFFu;
+            const uint32_t kind = s >> 29, payload = s & 0x1FFFFFFFu;     // graph_stream.h spelled out: its helpers here change the code object
             Fe29<F> r;
             if (kind == GRAPH_SRC_PREV) {
                 r = prev;
@@ -96,7 +84,7 @@ KERNEL void __launch_bounds__(256) k_graph_eval(const GraphJob *__restrict__ job
                 const GraphCol c = cols[payload & 0xFFFFFu];
                 int64_t rr = ((int64_t)row + rotations[payload >> 20]) % (int64_t)nrows;   // rem_euclid, graph_evaluator.rs:51-53
                 if (rr < 0) rr += (int64_t)nrows;
-                // a column enters as it lies in memory -- x * 2^256, "form 1" of the compiler (graph.hip), no lifting
+                // a column enters as it lies in memory -- x * 2^256, "form 1" of the compiler (graph_compile.h), no lifting
                 // product -- and a selector as the number one in that form (src/plonk/eval.rs:62)
                 if (c.kind == MIRA_COL_BOOL) {
                     Fe<S> one_r;
@@ -115,7 +103,7 @@ KERNEL void __launch_bounds__(256) k_graph_eval(const GraphJob *__restrict__ job
         for (uint32_t i = 0; i < ninstr; i++) {
             const uint32_t head = pc[0], dst = pc[1], bounds = pc[2];
             prev = v;
-            const uint32_t op = head & 0xFFu, K = head >> 8;
+            const uint32_t op = gop_op(head), K = gop_bias(head);
             const Fe29<F> a = fetch(pc[3], bounds & 0xFFFFu);
             if (op == GOP_ADD) { v = f29_add(a, fetch(pc[4], bounds >> 16)); pc += 5; }
             else if (op == GOP_SUB) { v = graph_sub(a, fetch(pc[4], bounds >> 16), K); pc += 5; }
