@@ -126,7 +126,7 @@ int mira_msm_batch_device(uint64_t handle, const void *d_scalars, size_t n, size
 /* Point-chunk sharding across GPUs (one process per GPU): each rank runs mira_msm_partial on
  * its chunk, the ranks all-gather the MIRA_PARTIAL_U64 words, and every rank combines.
  * `first` = index of the chunk's first base inside the registered key.  Every rank must make the
- * same choices: the same window width -- *window_bits on entry (4..16), or, if that is 0, the
+ * same choices: the same window width -- *window_bits on entry (4..20), or, if that is 0, the
  * mira_msm_set_window_bits value, or 16: a partial's width never depends on the chunk length,
  * which differs between ranks -- and either all or none with mira_msm_precompute'd keys (a handle
  * with tables answers with table-mode partials here whatever its chunk length, unless a width is
@@ -139,12 +139,20 @@ int mira_msm_combine(int curve, const uint64_t *partials /* nparts * MIRA_PARTIA
  * RCCL all-gather reads): nothing crosses PCIe before the exchange.  Words beyond the partial's windows are zero. */
 int mira_msm_partial_to_device(uint64_t handle, size_t first, const void *d_scalars, size_t n,
                                void *d_out_partial, int32_t *window_bits, int32_t *num_windows);
-/* Window width c (4..16) of every later commit over THIS key; 0 = let the planner choose from n and the
- * scalar statistics.  Per handle, so two caller threads working on two keys never see each other's choice. */
+/* Window width c (4..20) of every later commit over THIS key (CommitmentKey::commit, src/commitment.rs:78-87); 0 = let
+ * the planner choose from n and the scalar statistics.  Per handle, so two caller threads working on two keys never see each
+ * other's choice.  Widths of 17 to 20 bits commit on the plain path (never the GLV split, no table set) and need
+ * W * 2^(c-1) * 144 bytes of bucket workspace: 1 GB at c = 20 (13 windows of 2^19 buckets). */
 int mira_msm_set_handle_window_bits(uint64_t handle, int32_t c);
-/* Process-wide default width for keys without one of their own (tests, benchmarks; 0 = planner).  A process
+/* The widest window cmax (16..20) the planner and the width trials may pick for the commits of THIS key
+ * (CommitmentKey::commit, src/commitment.rs:78-87).  16, the default, changes nothing; 17..20 let the planner take a wide width
+ * on the plain path where its measured table puts it at least 2 % ahead (large commits: fewer windows, fewer additions per
+ * pair, W * 2^(c-1) * 144 bytes of bucket workspace).  mira_msm_plan_window_bits does not look at it. */
+int mira_msm_set_handle_max_window_bits(uint64_t handle, int32_t cmax);
+/* Process-wide default width (4..16) for keys without one of their own (tests, benchmarks; 0 = planner).  A process
  * whose threads want different widths uses the per-handle call above.  All ranks of a sharded MSM must use the
- * same c. */
+ * same c.  Wider windows cost W * 2^(c-1) * 144 bytes of bucket workspace per commit: they are a decision about one key
+ * (mira_msm_set_handle_window_bits, mira_msm_set_handle_max_window_bits), not the process. */
 int mira_msm_set_window_bits(int32_t c);
 /* The width the planner picks for a commit of n uniform scalars when it has no statistics of the data (a pure
  * function of n: every rank of a sharded MSM derives the same width from the same global length). */
@@ -207,6 +215,10 @@ int mira_msm_last_table_bits(int32_t *table_bits);
  * four block-groups (wave-level kernel) or lines (workgroup-level kernel) per workgroup hands them out through per-XCD counters;
  * tests set a small grid so that this path, its ranges without a home workgroup included, runs at sizes the CPU emulation reaches */
 #define MIRA_TUNE_NTT_GRID 19
+/* smallest window width whose commits take the two-level front of the wide windows (int32 digits, a coarse histogram and sort
+ * by the top 9 bits of the bucket, bucket counts from that output; csrc/msm_host.cuh); default 17, the first width whose bucket
+ * histogram does not fit LDS.  Tests set it low so that narrow widths run through that front at sizes the CPU emulation reaches */
+#define MIRA_TUNE_WIDE_FRONT_MIN_C 20
 int mira_set_tuning(int knob, int64_t value);
 
 /* Read a range of the registered key back in the reference layout (cache file writing,

@@ -31,10 +31,12 @@ SYMBOLS = [
     "mira_msm_register_bases_file", "mira_msm_save_bases_file", "mira_msm_partial_to_device", "mira_msm_set_handle_window_bits",
     "mira_trim", "mira_dev_mem_info", "mira_msm_plan_window_bits", "mira_lincomb_multi_device", "mira_dev_copy", "mira_msm_last_table_bits",
     "mira_graph_specialize", "mira_graph_is_specialized", "mira_graph_jit_source", "mira_graph_jit_compile_check",
+    "mira_msm_set_handle_max_window_bits",
 ]
 TUNE_STAGED_MIN_N, TUNE_TABLE_MIN_N, TUNE_PLAN_HIST_MIN_N, TUNE_NTT_MAX_LOG_LINE, TUNE_NTT_WAVE, TUNE_HOST_CHUNK_MIN_N, TUNE_NTT_SINGLE_TW_LOG, TUNE_NTT_FULL_TW_MAX_LOG, TUNE_TABLE_WIDTH, TUNE_JIT_LOADS_AHEAD, TUNE_MIN_SEGMENT, TUNE_GLV = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 TUNE_REDUCE_PIECES, TUNE_REDUCE_LAMBDA, TUNE_REDUCE_QUAD, TUNE_SHARED_MIN_N, TUNE_PASS_ENTRIES_LOG, TUNE_GLV_AUTO_MAX_LOG, TUNE_WIDTH_TRIALS = 12, 13, 14, 15, 16, 17, 18
 TUNE_NTT_GRID = 19
+TUNE_WIDE_FRONT_MIN_C = 20
 TABLE_GLV = 2   # mira_msm_precompute_ex(handle, MIRA_TABLE_GLV): the endomorphism copy of a key
 
 
@@ -118,7 +120,7 @@ class MiraLib:
             "mira_dev_sync": [], "mira_set_timing": [ctypes.c_int], "mira_get_timings": [vp, vp, ctypes.c_int],
             "mira_set_tuning": [ctypes.c_int, ctypes.c_int64],
             "mira_msm_register_bases_file": [ctypes.c_int, ctypes.c_char_p, u32, ctypes.c_int, vp], "mira_msm_save_bases_file": [u64, ctypes.c_char_p],
-            "mira_msm_partial_to_device": [u64, sz, vp, sz, vp, vp, vp], "mira_msm_set_handle_window_bits": [u64, i32],
+            "mira_msm_partial_to_device": [u64, sz, vp, sz, vp, vp, vp], "mira_msm_set_handle_window_bits": [u64, i32], "mira_msm_set_handle_max_window_bits": [u64, i32],
             "mira_trim": [sz, vp], "mira_dev_mem_info": [vp, vp], "mira_msm_plan_window_bits": [sz, vp],
             "mira_lincomb_multi_device": [ctypes.c_int, vp, sz, vp, sz, u64p, sz], "mira_dev_copy": [vp, vp, sz],
         }

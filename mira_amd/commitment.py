@@ -201,8 +201,14 @@ class CommitmentKey:
         return c.value, w.value
 
     def set_window_bits(self, c):
-        """Window width of every later commit over THIS key (4..16; 0 = planner): mira_msm_set_handle_window_bits."""
+        """Window width of every later commit over THIS key (4..20; 0 = planner): mira_msm_set_handle_window_bits.
+        Widths of 17 to 20 bits commit on the plain path and need W * 2^(c-1) * 144 bytes of bucket workspace."""
         self.lib.check(self.lib.c.mira_msm_set_handle_window_bits(self.handle, c))
+
+    def set_max_window_bits(self, cmax):
+        """Widest window (16..20; 16 = default) the planner and the width trials may pick for THIS key:
+        mira_msm_set_handle_max_window_bits.  Wide windows cut the additions of large commits for more bucket workspace."""
+        self.lib.check(self.lib.c.mira_msm_set_handle_max_window_bits(self.handle, cmax))
 
     def close(self):
         if getattr(self, "handle", None):

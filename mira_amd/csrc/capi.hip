@@ -195,8 +195,9 @@ static int msm_partial_locked(uint64_t handle, size_t first, const void *d_scala
     const int32_t width = requested_c ? requested_c : (sharded && forced_c == 0) ? 16 : forced_c;
     // the GLV split (glv.cuh): 2 n half-length scalars over the interleaved key; not for ranks of a sharded MSM (their partials
     // must have one shape whatever each rank's key holds) nor beside a table set
-    const bool glv_ok = !set && !table_mode && !sharded && n != 0 && n < (1ull << 30) && glv_possible(bs);
-    const MsmPlan p_plain = make_plan(n, width, 1, 0, (use_hist && bs.stat_kind == 0) ? stat_any : nullptr);
+    // (windows wider than 16 bits are for the plain path: a key forced to one, or whose planner picked one, never splits)
+    const MsmPlan p_plain = make_plan(n, width, 1, 0, (use_hist && bs.stat_kind == 0) ? stat_any : nullptr, 256, bs.max_c);
+    const bool glv_ok = !set && !table_mode && !sharded && n != 0 && n < (1ull << 30) && p_plain.c <= MSM_MAX_NARROW_C && glv_possible(bs);
     const MsmPlan p_split = glv_ok ? make_plan(2 * n, width, 1, 0, (use_hist && bs.stat_kind == 1) ? stat_any : nullptr, GLV_BITS) : p_plain;
     const bool glv = glv_ok && choose_glv(bs, p_plain, p_split, n) && glv_ready(bs);
     MsmPlan p = glv ? p_split : p_plain;
@@ -247,7 +248,7 @@ static int msm_partial_locked(uint64_t handle, size_t first, const void *d_scala
 
 static int combine_locked(int curve, const uint64_t *partials, size_t nparts, uint32_t c, uint32_t W, uint64_t out[8]) {
     if (curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) { set_error("unknown curve"); return MIRA_E_BAD_ARG; }
-    if (!partials || !out || nparts == 0 || c > 16 || W < 1 || W > MIRA_MAX_WINDOWS) { set_error("bad combine arguments"); return MIRA_E_BAD_ARG; }
+    if (!partials || !out || nparts == 0 || c > MSM_MAX_C || W < 1 || W > MIRA_MAX_WINDOWS) { set_error("bad combine arguments"); return MIRA_E_BAD_ARG; }
     std::vector<uint64_t> win((size_t)W * 16);
     const PartialShape sh{c, W, c ? c - 1 : 0, 1};
     on_curve(curve, [&](auto fb, auto) {
@@ -306,23 +307,22 @@ static int msm_batch_device_locked(uint64_t handle, const void *d_scalars, size_
         return MIRA_OK;
     }
     // the GLV split (glv.cuh) where the key has its endomorphism copy: 2 n half-length scalars per commitment, half the windows
-    bool glv = n < (1ull << 30) && glv_possible(bs);
+    bool glv = n < (1ull << 30) && (forced_c == 0 || forced_c <= (int32_t)MSM_MAX_NARROW_C) && glv_possible(bs);
     if (glv) {                                               // the planners' estimates for a batch of this shape decide (choose_glv)
         const uint32_t shape = (uint32_t)std::min<size_t>(count, 8);
-        glv = choose_glv(bs, make_plan(n, forced_c, shape, stride), make_plan(2 * n, forced_c, shape, stride, nullptr, GLV_BITS), n * shape) && glv_ready(bs);
+        const MsmPlan plain = make_batch_plan(n, forced_c, shape, stride, 256, bs.max_c);
+        glv = plain.c <= MSM_MAX_NARROW_C && choose_glv(bs, plain, make_plan(2 * n, forced_c, shape, stride, nullptr, GLV_BITS), n * shape) && glv_ready(bs);
     }
     const size_t nv = glv ? 2 * n : n;
     const uint32_t bits = glv ? GLV_BITS : 256;
-    MsmPlan p1 = make_plan(nv, forced_c, 1, 0, nullptr, bits);
-    // per launch: W_total * B counters <= 2^21 (three-launch scan) and n * W_total entries < 2^32
-    size_t per = std::max<size_t>(1, std::min<size_t>((size_t)((1ull << 21) / ((uint64_t)p1.W * p1.B)),
-                                                      (size_t)(((1ull << 32) - 1) / ((uint64_t)nv * p1.W))));
+    const uint32_t cmax = glv ? MSM_MAX_NARROW_C : bs.max_c;
+    const size_t per = batch_per_launch(nv, forced_c, bits, cmax);
     std::vector<uint64_t> win;
     for (size_t done = 0; done < count; done += per) {
         const size_t cnt = std::min(per, count - done);
-        MsmPlan p = make_plan(nv, forced_c, (uint32_t)cnt, stride, nullptr, bits);
+        MsmPlan p = make_batch_plan(nv, forced_c, (uint32_t)cnt, stride, bits, cmax);
         Bases::WidthTrial *trial = forced_c == 0 ? trial_for(bs, n, (uint32_t)cnt, (glv ? 1u : 0u) | (h_batch ? 2u : 0u), p.c) : nullptr;
-        if (trial && trial_width(*trial) != p.c && (uint64_t)((bits + trial_width(*trial) - 1) / trial_width(*trial)) * cnt * (1ull << (trial_width(*trial) - 1)) <= (1ull << 21))
+        if (trial && trial_width(*trial) != p.c && (uint64_t)((bits + trial_width(*trial) - 1) / trial_width(*trial)) * cnt * (1ull << (trial_width(*trial) - 1)) <= SCAN_MAX_COUNTERS)
             p = make_plan(nv, (int32_t)trial_width(*trial), (uint32_t)cnt, stride, nullptr, bits);      // (a width whose counters one scan takes)
         p.glv = glv; p.glv_bases = glv ? bs.glv : nullptr;
         p.h_batch = h_batch ? h_batch + done : nullptr;
@@ -549,7 +549,7 @@ int mira_msm_partial_device(uint64_t handle, size_t first, const void *d_scalars
                             int32_t *window_bits, int32_t *num_windows) {
     std::lock_guard<std::mutex> lk(g_lock);
     if (!out_partial || !window_bits || !num_windows) { set_error("null output"); return MIRA_E_BAD_ARG; }
-    if (*window_bits != 0 && (*window_bits < 4 || *window_bits > 16)) { set_error("window_bits must be 0 or 4..16"); return MIRA_E_BAD_ARG; }
+    if (*window_bits != 0 && (*window_bits < 4 || *window_bits > (int32_t)MSM_MAX_C)) { set_error("window_bits must be 0 or 4..20"); return MIRA_E_BAD_ARG; }
     PartialShape sh;
     int rc = msm_partial_locked(handle, first, d_scalars, n, out_partial, &sh, true, *window_bits);
     if (rc) return rc;
@@ -561,7 +561,7 @@ int mira_msm_combine(int curve, const uint64_t *partials, size_t nparts, int32_t
 }
 int mira_set_tuning(int knob, int64_t value) {
     std::lock_guard<std::mutex> lk(g_lock);
-    if (knob < 0 || knob > MIRA_TUNE_NTT_GRID || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
+    if (knob < 0 || knob > MIRA_TUNE_WIDE_FRONT_MIN_C || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
     g.tune[knob] = value;
     return MIRA_OK;
 }
@@ -592,17 +592,25 @@ int mira_msm_set_window_bits(int32_t c) {
 
 int mira_msm_set_handle_window_bits(uint64_t handle, int32_t c) {
     std::lock_guard<std::mutex> lk(g_lock);
-    if (c != 0 && (c < 4 || c > 16)) { set_error("window bits must be 0 or in [4,16]"); return MIRA_E_BAD_ARG; }
+    if (c != 0 && (c < 4 || c > (int32_t)MSM_MAX_C)) { set_error("window bits must be 0 or in [4,20]"); return MIRA_E_BAD_ARG; }
     auto it = g_bases.find(handle);
     if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
     it->second.forced_c = c;
+    return MIRA_OK;
+}
+int mira_msm_set_handle_max_window_bits(uint64_t handle, int32_t cmax) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (cmax < (int32_t)MSM_MAX_NARROW_C || cmax > (int32_t)MSM_MAX_C) { set_error("max window bits must be in [16,20]"); return MIRA_E_BAD_ARG; }
+    auto it = g_bases.find(handle);
+    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
+    if (it->second.max_c != (uint32_t)cmax) { it->second.max_c = (uint32_t)cmax; it->second.trials.clear(); }   // the width trials start again
     return MIRA_OK;
 }
 int mira_msm_partial_to_device(uint64_t handle, size_t first, const void *d_scalars, size_t n, void *d_out_partial,
                                int32_t *window_bits, int32_t *num_windows) {
     std::lock_guard<std::mutex> lk(g_lock);
     if (!d_out_partial || !window_bits || !num_windows) { set_error("null output"); return MIRA_E_BAD_ARG; }
-    if (*window_bits != 0 && (*window_bits < 4 || *window_bits > 16)) { set_error("window_bits must be 0 or 4..16"); return MIRA_E_BAD_ARG; }
+    if (*window_bits != 0 && (*window_bits < 4 || *window_bits > (int32_t)MSM_MAX_C)) { set_error("window_bits must be 0 or 4..20"); return MIRA_E_BAD_ARG; }
     int rc = ensure_ctx();
     if (rc) return rc;
     RT_CHECK(rt_memset(d_out_partial, 0, MIRA_PARTIAL_U64 * 8, g.stream));     // words beyond the partial's windows (and an empty chunk) read as the identity

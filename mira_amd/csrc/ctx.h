@@ -145,7 +145,8 @@ struct Bases {
     size_t n;
     void *d = nullptr;
     bool owned = false;
-    int32_t forced_c = 0;     // mira_msm_set_handle_window_bits: this key's window width, 0 = planner / process default
+    int32_t forced_c = 0;     // mira_msm_set_handle_window_bits: this key's window width (4 .. 20), 0 = planner / process default
+    uint32_t max_c = 16;      // mira_msm_set_handle_max_window_bits: the widest window the planner and the width trials may pick for this key
     void *tables = nullptr;   // fixed-base window tables 2^(table_c w) P_i, w < table_w (table_kernels.cuh: 20 or 22 bits), or null
     uint32_t table_c = 0, table_w = 0;
     // shared-bucket table sets (8 .. 16 bits, msm_host.cuh): any number of widths beside each other, each W x the key
@@ -179,6 +180,14 @@ void tm_end();
 
 static inline size_t tuned(int knob, size_t dflt) { return g.tune[knob] < 0 ? dflt : (size_t)g.tune[knob]; }
 static inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// Window widths of the per-window path.  Up to 16 bits the digits are int16 and the bucket histogram of a window fits LDS; 17 to
+// 20 bits (plain path only, never the GLV split) take int32 digits and the two-level front (msm_host.cuh).  Widths from
+// MIRA_TUNE_WIDE_FRONT_MIN_C on take that front (default 17; tests drive narrow widths through it).
+static constexpr uint32_t MSM_MAX_C = 20, MSM_MAX_NARROW_C = 16;
+static inline uint32_t wide_front_min_c() { return (uint32_t)tuned(MIRA_TUNE_WIDE_FRONT_MIN_C, MSM_MAX_NARROW_C + 1); }
+// the bucket counters one launch sequence scans (k_scan_b: 1024 lanes over up to 8 block sums each): 13 windows of 2^19 buckets
+static constexpr uint64_t SCAN_MAX_COUNTERS = (uint64_t)1 << 24;
 
 #ifndef MSM_HIST_WGS
 #define MSM_HIST_WGS 256      // workgroups of k_hist / k_scatter over one chunk: one per CU -- every workgroup zeroes and flushes a whole bucket set
@@ -220,6 +229,13 @@ struct PartialShape { uint32_t c = 0, W = 0, cb = 0, P = 1; };
 
 // Shape of the bucket reduction of a plan.  Quads for phase A while the chunks are few (the chain of dependent additions is
 // what takes the time: chunks of four buckets), single lanes in chunks of eight once they fill the SIMDs.
+// SMALL_WG: the workgroup sizes of the CPU emulation (its lanes are OS threads); tests ask for the device's shapes with false.
+#ifdef MIRA_CPU_EMU
+static constexpr bool REDUCE_SMALL_WG = true;
+#else
+static constexpr bool REDUCE_SMALL_WG = false;
+#endif
+template <bool SMALL_WG = REDUCE_SMALL_WG>
 static inline void plan_reduction(MsmPlan &p, uint32_t want_pieces) {
     p.nsets = p.shared ? p.count : p.Wt;
     p.cb = p.c - 1;
@@ -230,12 +246,12 @@ static inline void plan_reduction(MsmPlan &p, uint32_t want_pieces) {
     // k_set_finish holds the 2^gamma nodes of a set in LDS, (kappa + 2) points each: with 128 quads per workgroup (kappa = 7) that is
     // gamma <= 6, i.e. eta <= 13 -- a 16-bit set in chunks of two buckets would need more: wider chunks there (tuning knobs included)
     while (p.rquad && p.cb - p.lambda > 13) p.lambda++;
+    // ... and with 256 lanes per workgroup (kappa = 8) gamma <= 6, i.e. eta <= 14: the 17- to 20-bit windows (2^16 .. 2^19 buckets)
+    // take chunks of 8 .. 32 buckets (no width up to 16 reaches this)
+    while (!p.rquad && p.cb - p.lambda > 14) p.lambda++;
     const uint32_t eta = p.cb - p.lambda;
-#ifdef MIRA_CPU_EMU
-    p.kappa = std::min<uint32_t>(eta, 3);                                      // emulated lanes are OS threads: small workgroups, a taller second tree
-#else
-    p.kappa = std::min<uint32_t>(eta, p.rquad ? (eta > 12 ? 7 : 6) : 8);      // 64 (128) quads or 256 lanes per workgroup
-#endif
+    if (SMALL_WG) p.kappa = std::min<uint32_t>(eta, 3);                           // emulated lanes are OS threads: small workgroups, a taller second tree
+    else p.kappa = std::min<uint32_t>(eta, p.rquad ? (eta > 12 ? 7 : 6) : 8);      // 64 (128) quads or 256 lanes per workgroup
     p.gamma = eta - p.kappa;
     p.pieces = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(want_pieces, 8), std::max<uint32_t>(1, p.cb / 2)));
     p.m = 1u << p.lambda;

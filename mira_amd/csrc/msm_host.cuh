@@ -106,18 +106,33 @@ static int msm_launch_body(const Bases &bs, size_t first, const void *d_scalars,
     for (size_t k = 0, lo = 0; k < ends.size(); lo = ends[k++]) nmax = std::max(nmax, ends[k] - lo);
     nmax *= mult;
     const size_t entries_max = nmax * p.Wt;
-    if ((rc = g.digits.ensure(entries_max * 2))) return rc;
-    if ((rc = g.counts.ensure(((size_t)p.NB + 1) * 4))) return rc;
+    // the two-level front of the wide windows (below): int32 digits, W * CB coarse counters behind the NB bucket counters
+    const bool wide = (p.c > MSM_MAX_NARROW_C || p.c >= wide_front_min_c()) && !p.glv && !p.shared;
+    if (p.c > MSM_MAX_C || (p.c > MSM_MAX_NARROW_C && !wide)) {
+        set_error("windows wider than 16 bits are for the plain per-window path only"); return MIRA_E_UNSUPPORTED;
+    }
+    const uint32_t wide_fine_bits = (p.c - 1) - std::min<uint32_t>(p.c - 1, 9), wide_CB = p.B >> wide_fine_bits;   // <= STAGE_MAX_BINS1 coarse bins per window
+    const uint32_t wide_NCB = wide ? p.Wt * wide_CB : 0u;
+    // the coarse counters start at the first 16-byte boundary behind the NB + 1 bucket counters (k_scan_c<SCAN_OWN_PREFIX> reads them
+    // with 16-byte loads; NB is a multiple of 8)
+    const size_t wide_coarse_at = ((size_t)p.NB + 1 + 3) / 4 * 4;
+    if ((uint64_t)p.NB > SCAN_MAX_COUNTERS) { set_error("window configuration exceeds the scan capacity"); return MIRA_E_UNSUPPORTED; }
+    const uint32_t scan_blocks = ceil_div(p.NB, SCAN_TILE);
+    if ((rc = g.digits.ensure(entries_max * (wide ? 4 : 2)))) return rc;
+    if ((rc = g.counts.ensure((wide ? wide_coarse_at + wide_NCB + 1 : (size_t)p.NB + 1) * 4))) return rc;
     if ((rc = g.offsets.ensure(((size_t)p.NB + 1) * 4))) return rc;
     if ((rc = g.cursor.ensure(((size_t)p.NB + 1) * 4))) return rc;
-    const uint32_t scan_blocks = ceil_div(p.NB, SCAN_TILE);
-    if (scan_blocks > 1024) { set_error("window configuration exceeds the scan capacity"); return MIRA_E_UNSUPPORTED; }
-    if ((rc = g.block_sums.ensure(1024 * 4))) return rc;
+    if ((rc = g.block_sums.ensure((size_t)std::max<uint32_t>(1024, scan_blocks) * 4))) return rc;
     if ((rc = g.sorted_idx.ensure(entries_max * 4 + 8 + ACC_STAGE_PAD))) return rc;
     const size_t staged_min_n = tuned(MIRA_TUNE_STAGED_MIN_N, (size_t)1 << 19);
-    if (nmax * p.count >= staged_min_n && p.c >= 9) {
+    if (nmax * p.count >= staged_min_n && p.c >= 9 && !wide) {
         if ((rc = g.part.ensure(entries_max * 8 + 8))) return rc;
         if ((rc = g.coarse_offsets.ensure(((size_t)p.Wt * 512 + 1) * 4))) return rc;
+    }
+    if (wide) {
+        if ((rc = g.part.ensure(entries_max * 8 + 8))) return rc;
+        if ((rc = g.coarse_offsets.ensure(((size_t)wide_NCB + 1) * 4))) return rc;
+        if ((rc = g.fine_cursor.ensure(((size_t)wide_NCB + 1) * 4))) return rc;      // the coarse cursors of level 1
     }
     if ((rc = g.bucket_sums.ensure((size_t)p.NB * XYZZ29_BYTES))) return rc;
     if ((rc = g.head_part.ensure((size_t)p.T * XYZZ29_BYTES))) return rc;
@@ -150,6 +165,23 @@ static int msm_launch_body(const Bases &bs, size_t first, const void *d_scalars,
     // coarse bin of the staged sort = top 8 bits of the bucket id (6..9 measured equal)
     const uint32_t fine_bits = (p.c - 1) - std::min<uint32_t>(p.c - 1, 8);
     const uint32_t CB = p.B >> fine_bits;                                       // <= 256 coarse bins per window
+    // exclusive scan of N counters into offsets / cursor with the by-products of k_scan_c (null: skipped)
+    auto scan = [&](const uint32_t *counts, uint32_t N, uint32_t *offsets, uint32_t *cursor, uint32_t *cursor1, uint32_t cursor1_bits, uint32_t *plan_out,
+                    unsigned char *markers) {
+        const uint32_t blocks = ceil_div(N, SCAN_TILE);
+        if (blocks <= SCAN_SOLO_TILES) {                     // few buckets: one workgroup scans them all, one launch instead of three
+            LAUNCH_BARRIER(k_scan_c<SCAN_SOLO>, 1, SCAN_BLOCK, 0, st, counts, N, reinterpret_cast<const uint32_t *>(g.block_sums.p), offsets, cursor, cursor1,
+                           cursor1_bits, plan_out, p.lanes, p.L, heavy_count, markers);
+        } else if (blocks <= SCAN_OWN_PREFIX_TILES) {        // the bucket counts of the small commits: every workgroup sums what lies in front of it
+            LAUNCH_BARRIER(k_scan_c<SCAN_OWN_PREFIX>, blocks, SCAN_BLOCK, 0, st, counts, N, reinterpret_cast<const uint32_t *>(g.block_sums.p), offsets, cursor,
+                           cursor1, cursor1_bits, plan_out, p.lanes, p.L, heavy_count, markers);
+        } else {
+            LAUNCH_BARRIER(k_scan_a, blocks, SCAN_BLOCK, 0, st, counts, N, reinterpret_cast<uint32_t *>(g.block_sums.p));
+            LAUNCH_BARRIER(k_scan_b, 1, 1024, 0, st, reinterpret_cast<uint32_t *>(g.block_sums.p), blocks);
+            LAUNCH_BARRIER(k_scan_c<SCAN_BLOCK_SUMS>, blocks, SCAN_BLOCK, 0, st, counts, N, reinterpret_cast<const uint32_t *>(g.block_sums.p), offsets, cursor,
+                           cursor1, cursor1_bits, plan_out, p.lanes, p.L, heavy_count, markers);
+        }
+    };
 
     // No clearing passes: k_digits zeroes the bucket counters, k_scan_c the heavy-run counters and (first
     // chunk) the identity marker of every bucket without entries, every segment of k_accumulate writes its tail key.
@@ -190,53 +222,66 @@ static int msm_launch_body(const Bases &bs, size_t first, const void *d_scalars,
         // histogram / scatter tiling of this chunk: about one workgroup per CU, at least 1024 points per tile
         const uint32_t tile = (std::max<uint32_t>(1024, ceil_div(nc, std::max<uint32_t>(1, MSM_HIST_WGS / p.Wt))) + 1023) / 1024 * 1024, ntiles = ceil_div(nc, tile);
         const bool staged = nc * p.count >= staged_min_n && p.c >= 9;   // a batch is count MSMs' worth of entries
-        if (p.glv)
-            LAUNCH((k_digits<FS, true>), dim3(ceil_div(ns, MSM_DIGITS_BLOCK), p.count), MSM_DIGITS_BLOCK, 0, st, sc, (uint32_t)ns, stride_k, p.c, p.W,
-                   reinterpret_cast<int16_t *>(g.digits.p), reinterpret_cast<uint32_t *>(g.counts.p), p.NB + 1, hist, hist_clear);
-        else
-        LAUNCH(k_digits<FS>, dim3(ceil_div(nc, MSM_DIGITS_BLOCK), p.count), MSM_DIGITS_BLOCK, 0, st, sc, (uint32_t)nc, stride_k, p.c, p.W,
-               reinterpret_cast<int16_t *>(g.digits.p), reinterpret_cast<uint32_t *>(g.counts.p), p.NB + 1, hist, hist_clear);
-        tm_mark("digits");
-        LAUNCH_BARRIER_FLEX(k_hist, dim3(ntiles, p.Wt), 1024, (size_t)p.B * 4, st, reinterpret_cast<const int16_t *>(g.digits.p), (uint32_t)nc,
-                       p.B, tile, reinterpret_cast<uint32_t *>(g.counts.p), wgroup);
-        tm_mark("hist");
-        if (scan_blocks <= SCAN_SOLO_TILES) {                 // few buckets: one workgroup scans them all, one launch instead of three
-            LAUNCH_BARRIER(k_scan_c<SCAN_SOLO>, 1, SCAN_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.counts.p), p.NB,
-                           reinterpret_cast<const uint32_t *>(g.block_sums.p), reinterpret_cast<uint32_t *>(g.offsets.p),
-                           reinterpret_cast<uint32_t *>(g.cursor.p), staged ? reinterpret_cast<uint32_t *>(g.coarse_offsets.p) : no_u32, fine_bits,
-                           plan, p.lanes, p.L, heavy_count, add ? no_u8 : reinterpret_cast<unsigned char *>(g.bucket_sums.p));
-        } else if (scan_blocks <= SCAN_OWN_PREFIX_TILES) {    // the bucket counts of the small commits: every workgroup sums what lies in front of it
-            LAUNCH_BARRIER(k_scan_c<SCAN_OWN_PREFIX>, scan_blocks, SCAN_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.counts.p), p.NB,
-                           reinterpret_cast<const uint32_t *>(g.block_sums.p), reinterpret_cast<uint32_t *>(g.offsets.p),
-                           reinterpret_cast<uint32_t *>(g.cursor.p), staged ? reinterpret_cast<uint32_t *>(g.coarse_offsets.p) : no_u32, fine_bits,
-                           plan, p.lanes, p.L, heavy_count, add ? no_u8 : reinterpret_cast<unsigned char *>(g.bucket_sums.p));
-        } else {
-        LAUNCH_BARRIER(k_scan_a, scan_blocks, SCAN_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.counts.p), p.NB,
-                       reinterpret_cast<uint32_t *>(g.block_sums.p));
-        LAUNCH_BARRIER(k_scan_b, 1, 1024, 0, st, reinterpret_cast<uint32_t *>(g.block_sums.p), scan_blocks);
-        LAUNCH_BARRIER(k_scan_c<SCAN_BLOCK_SUMS>, scan_blocks, SCAN_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.counts.p), p.NB,
-                       reinterpret_cast<const uint32_t *>(g.block_sums.p), reinterpret_cast<uint32_t *>(g.offsets.p),
-                       reinterpret_cast<uint32_t *>(g.cursor.p), staged ? reinterpret_cast<uint32_t *>(g.coarse_offsets.p) : no_u32, fine_bits,
-                       plan, p.lanes, p.L, heavy_count, add ? no_u8 : reinterpret_cast<unsigned char *>(g.bucket_sums.p));
-        }
-        tm_mark("scan");
-        // sort: LDS-staged two-level partition for large inputs (bursts of consecutive entries), the
-        // single-level scatter otherwise (small inputs: the tile structure buys nothing there)
-        if (staged) {
-            if (p.shared)
-                LAUNCH_BARRIER((k_stage1<int16_t, true, STAGE_TILE_PW>), dim3(ceil_div(nc, STAGE_TILE_PW), p.Wt), 1024, (size_t)STAGE_TILE_PW * 8, st, reinterpret_cast<const int16_t *>(g.digits.p),
-                                    (uint32_t)nc, p.B, fine_bits, CB, idx_stride, idx_first, wgroup, reinterpret_cast<uint32_t *>(g.coarse_offsets.p), reinterpret_cast<U2 *>(g.part.p));
-            else
-                LAUNCH_BARRIER((k_stage1<int16_t, false, STAGE_TILE_PW>), dim3(ceil_div(nc, STAGE_TILE_PW), p.Wt), 1024, (size_t)STAGE_TILE_PW * 8, st, reinterpret_cast<const int16_t *>(g.digits.p),
-                                    (uint32_t)nc, p.B, fine_bits, CB, 0u, 0u, 1u, reinterpret_cast<uint32_t *>(g.coarse_offsets.p), reinterpret_cast<U2 *>(g.part.p));
+        unsigned char *markers = add ? no_u8 : reinterpret_cast<unsigned char *>(g.bucket_sums.p);   // (first chunk) identity markers of the empty buckets
+        if (wide) {
+            // Windows of 17 bits and more: 2^16 .. 2^19 bucket counters per window do not fit LDS (k_hist / k_scatter hold B of them).
+            // The front of the wide tables (msm_launch_table) per window instead: a histogram and a level-1 sort by coarse bin (the top
+            // 9 bits of the bucket), the bucket counts from that coarse-sorted stream, their scan, and level 2 by bucket.
+            uint32_t *fine_counts = reinterpret_cast<uint32_t *>(g.counts.p), *coarse_counts = fine_counts + wide_coarse_at;
+            uint32_t *coarse_ofs = reinterpret_cast<uint32_t *>(g.coarse_offsets.p), *coarse_cur = reinterpret_cast<uint32_t *>(g.fine_cursor.p);
+            LAUNCH((k_digits<FS, false, int32_t>), dim3(ceil_div(nc, MSM_DIGITS_BLOCK), p.count), MSM_DIGITS_BLOCK, 0, st, sc, (uint32_t)nc, stride_k, p.c, p.W,
+                   reinterpret_cast<int32_t *>(g.digits.p), fine_counts, (uint32_t)(wide_coarse_at + wide_NCB + 1), hist, hist_clear);
+            tm_mark("digits");
+            // ~4096 workgroups in all (the k_hist tiling, one workgroup per CU, left the coarse histogram at 1 TB/s: 3.3 ms of a 2^26 commit)
+            const uint32_t ctile = (std::max<uint32_t>(1024, ceil_div(nc, std::max<uint32_t>(1, 4096 / p.Wt))) + 1023) / 1024 * 1024;
+            LAUNCH_BARRIER_FLEX(k_thist_coarse, dim3(ceil_div(nc, ctile), p.Wt), 512, 0, st, reinterpret_cast<const int32_t *>(g.digits.p), (uint32_t)nc, ctile,
+                                wide_fine_bits, coarse_counts, wide_CB, wide_CB);
+            tm_mark("hist");
+            scan(coarse_counts, wide_NCB, coarse_ofs, coarse_cur, no_u32, 0u, no_u32, no_u8);
+            tm_mark("scan");
+            LAUNCH_BARRIER((k_stage1<int32_t, false, STAGE_TILE>), dim3(ceil_div(nc, STAGE_TILE), p.Wt), 1024, (size_t)STAGE_TILE * 8, st,
+                           reinterpret_cast<const int32_t *>(g.digits.p), (uint32_t)nc, p.B, wide_fine_bits, wide_CB, 0u, 0u, 1u, coarse_cur, reinterpret_cast<U2 *>(g.part.p));
             tm_mark("sort_level1");
-            LAUNCH_BARRIER((k_stage2<STAGE_TILE_PW, STAGE_MAX_KEYS2_PW>), ceil_div(entries, STAGE_TILE_PW), 1024, (size_t)STAGE_TILE_PW * 6, st, reinterpret_cast<const U2 *>(g.part.p),
-                                reinterpret_cast<const uint32_t *>(g.offsets.p) + p.NB, fine_bits, reinterpret_cast<uint32_t *>(g.cursor.p),
-                                reinterpret_cast<uint32_t *>(g.sorted_idx.p));
-        } else
-            LAUNCH_BARRIER_FLEX(k_scatter, dim3(ntiles, p.Wt), 1024, (size_t)p.B * 4, st, reinterpret_cast<const int16_t *>(g.digits.p),
-                       (uint32_t)nc, p.B, tile, reinterpret_cast<uint32_t *>(g.cursor.p), reinterpret_cast<uint32_t *>(g.sorted_idx.p), wgroup, idx_stride, idx_first);
-        tm_mark("scatter");
+            const uint32_t *coarse_total = coarse_ofs + wide_NCB;
+            LAUNCH_BARRIER_FLEX(k_stage2_count, ceil_div(entries, STAGE_TILE), 1024, 0, st, reinterpret_cast<const U2 *>(g.part.p), coarse_total, wide_fine_bits, fine_counts);
+            tm_mark("bucket_count");
+            scan(fine_counts, p.NB, reinterpret_cast<uint32_t *>(g.offsets.p), reinterpret_cast<uint32_t *>(g.cursor.p), no_u32, 0u, plan, markers);
+            tm_mark("bucket_count_scan");
+            LAUNCH_BARRIER((k_stage2<STAGE_TILE, STAGE_MAX_KEYS2>), ceil_div(entries, STAGE_TILE), 1024, (size_t)STAGE_TILE * 6, st, reinterpret_cast<const U2 *>(g.part.p),
+                           coarse_total, wide_fine_bits, reinterpret_cast<uint32_t *>(g.cursor.p), reinterpret_cast<uint32_t *>(g.sorted_idx.p));
+            tm_mark("sort_level2");
+        } else {
+            if (p.glv)
+                LAUNCH((k_digits<FS, true>), dim3(ceil_div(ns, MSM_DIGITS_BLOCK), p.count), MSM_DIGITS_BLOCK, 0, st, sc, (uint32_t)ns, stride_k, p.c, p.W,
+                       reinterpret_cast<int16_t *>(g.digits.p), reinterpret_cast<uint32_t *>(g.counts.p), p.NB + 1, hist, hist_clear);
+            else
+            LAUNCH(k_digits<FS>, dim3(ceil_div(nc, MSM_DIGITS_BLOCK), p.count), MSM_DIGITS_BLOCK, 0, st, sc, (uint32_t)nc, stride_k, p.c, p.W,
+                   reinterpret_cast<int16_t *>(g.digits.p), reinterpret_cast<uint32_t *>(g.counts.p), p.NB + 1, hist, hist_clear);
+            tm_mark("digits");
+            LAUNCH_BARRIER_FLEX(k_hist, dim3(ntiles, p.Wt), 1024, (size_t)p.B * 4, st, reinterpret_cast<const int16_t *>(g.digits.p), (uint32_t)nc,
+                           p.B, tile, reinterpret_cast<uint32_t *>(g.counts.p), wgroup);
+            tm_mark("hist");
+            scan(reinterpret_cast<const uint32_t *>(g.counts.p), p.NB, reinterpret_cast<uint32_t *>(g.offsets.p), reinterpret_cast<uint32_t *>(g.cursor.p),
+                 staged ? reinterpret_cast<uint32_t *>(g.coarse_offsets.p) : no_u32, fine_bits, plan, markers);
+            tm_mark("scan");
+            // sort: LDS-staged two-level partition for large inputs (bursts of consecutive entries), the
+            // single-level scatter otherwise (small inputs: the tile structure buys nothing there)
+            if (staged) {
+                if (p.shared)
+                    LAUNCH_BARRIER((k_stage1<int16_t, true, STAGE_TILE_PW>), dim3(ceil_div(nc, STAGE_TILE_PW), p.Wt), 1024, (size_t)STAGE_TILE_PW * 8, st, reinterpret_cast<const int16_t *>(g.digits.p),
+                                        (uint32_t)nc, p.B, fine_bits, CB, idx_stride, idx_first, wgroup, reinterpret_cast<uint32_t *>(g.coarse_offsets.p), reinterpret_cast<U2 *>(g.part.p));
+                else
+                    LAUNCH_BARRIER((k_stage1<int16_t, false, STAGE_TILE_PW>), dim3(ceil_div(nc, STAGE_TILE_PW), p.Wt), 1024, (size_t)STAGE_TILE_PW * 8, st, reinterpret_cast<const int16_t *>(g.digits.p),
+                                        (uint32_t)nc, p.B, fine_bits, CB, 0u, 0u, 1u, reinterpret_cast<uint32_t *>(g.coarse_offsets.p), reinterpret_cast<U2 *>(g.part.p));
+                tm_mark("sort_level1");
+                LAUNCH_BARRIER((k_stage2<STAGE_TILE_PW, STAGE_MAX_KEYS2_PW>), ceil_div(entries, STAGE_TILE_PW), 1024, (size_t)STAGE_TILE_PW * 6, st, reinterpret_cast<const U2 *>(g.part.p),
+                                    reinterpret_cast<const uint32_t *>(g.offsets.p) + p.NB, fine_bits, reinterpret_cast<uint32_t *>(g.cursor.p),
+                                    reinterpret_cast<uint32_t *>(g.sorted_idx.p));
+            } else
+                LAUNCH_BARRIER_FLEX(k_scatter, dim3(ntiles, p.Wt), 1024, (size_t)p.B * 4, st, reinterpret_cast<const int16_t *>(g.digits.p),
+                           (uint32_t)nc, p.B, tile, reinterpret_cast<uint32_t *>(g.cursor.p), reinterpret_cast<uint32_t *>(g.sorted_idx.p), wgroup, idx_stride, idx_first);
+            tm_mark("scatter");
+        }
         if (add)
             LAUNCH((k_accumulate<F, true>), ceil_div(p.T, ACC_BLOCK), ACC_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.sorted_idx.p),
                    reinterpret_cast<const uint32_t *>(g.offsets.p), p.NB, bases, (const uint32_t *)plan,
@@ -327,6 +372,7 @@ template <class F, class FS> static int curve_init() {
     RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage1<int16_t, false, STAGE_TILE_PW>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_TILE_PW * 8));   // + 10 KiB static
     RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage1<int32_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_TILE * 8));
+    RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage1<int32_t, false, STAGE_TILE>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_TILE * 8));   // the wide windows
     RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage1<int16_t, true, STAGE_TILE_PW>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_TILE_PW * 8));
     RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage2<STAGE_TILE, STAGE_MAX_KEYS2>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_TILE * 6));   // + 52 KiB static
     RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage2<STAGE_TILE_PW, STAGE_MAX_KEYS2_PW>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_TILE_PW * 6));
@@ -451,7 +497,7 @@ static int msm_launch_table(const Bases &bs, size_t first, const void *d_scalars
            reinterpret_cast<int32_t *>(g.digits.p));
     tm_mark("digits");
     LAUNCH_BARRIER_FLEX(k_thist_coarse, dim3(ntiles, TABLE_W), 512, 0, st, reinterpret_cast<const int32_t *>(g.digits.p), (uint32_t)n, tile, TABLE_FINE_BITS,
-                        reinterpret_cast<uint32_t *>(g.counts.p));
+                        reinterpret_cast<uint32_t *>(g.counts.p), TABLE_CB, 0u);
     tm_mark("hist");
     LAUNCH_BARRIER(k_scan_a, 1, SCAN_BLOCK, 0, st, reinterpret_cast<const uint32_t *>(g.counts.p), TABLE_CB, reinterpret_cast<uint32_t *>(g.block_sums.p));
     LAUNCH_BARRIER(k_scan_b, 1, 1024, 0, st, reinterpret_cast<uint32_t *>(g.block_sums.p), 1u);

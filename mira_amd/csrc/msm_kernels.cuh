@@ -2,7 +2,8 @@
 // called by CommitmentKey::commit (reference src/commitment.rs:78-87).
 //
 // Pipeline (all on one HIP stream, no host round trip until the W window sums come back):
-//   k_digits      scalar (Montgomery) -> canonical integer -> W signed c-bit digits (int16)
+//   k_digits      scalar (Montgomery) -> canonical integer -> W signed c-bit digits (int16; int32 for
+//                 the two-level front of 17- to 20-bit windows, msm_host.cuh)
 //   k_hist        per (window, point-tile) workgroup: bucket histogram staged in LDS
 //                 (2^(c-1) counters = 128 KiB at c = 16), flushed with coalesced atomics
 //   k_scan_*      exclusive scan of the W * 2^(c-1) counters
@@ -53,9 +54,10 @@ static constexpr uint32_t HEAVY_SUB = 64;    // partials per stage-A sub-job of 
 // own read the scalars a second time and cost a launch, a memset and a copy: 30-50 us per commit).
 // hist_clear = the OTHER of the two histogram buffers, zeroed for the next commit.
 // GLV (glv.cuh): every scalar becomes TWO half-length ones, columns 2 i and 2 i + 1 of a digit matrix of 2 n columns.
-template <class FS, bool GLV = false>
+// DIGIT: int16_t up to 16-bit windows; int32_t for the wider ones of the plain path (the GLV split stays int16).
+template <class FS, bool GLV = false, class DIGIT = int16_t>
 KERNEL void k_digits(const unsigned char *__restrict__ scalars, uint32_t n, uint64_t stride, uint32_t c, uint32_t W,
-                     int16_t *__restrict__ digits, uint32_t *__restrict__ counts, uint32_t ncounts,
+                     DIGIT *__restrict__ digits, uint32_t *__restrict__ counts, uint32_t ncounts,
                      uint32_t *__restrict__ hist, uint32_t *__restrict__ hist_clear) {
     __shared__ uint32_t bins[256];
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -74,10 +76,11 @@ KERNEL void k_digits(const unsigned char *__restrict__ scalars, uint32_t n, uint
         const uint32_t b = blockIdx.y;                   // MSM of the batch: its windows are b*W .. b*W + W-1
         Fe<FS> s = fe_from_mont(fe_load<FS>(scalars + ((size_t)b * stride + i) * 32));
         if constexpr (GLV) {
+            static_assert(sizeof(DIGIT) == 2, "the halves of the GLV split take int16 digits");
             uint32_t h[2][5];
             bool neg[2];
             glv_split<FS>(s.l, h[0], h[1], neg[0], neg[1]);
-            int16_t *dg = digits + (size_t)b * W * (2 * (size_t)n);
+            DIGIT *dg = digits + (size_t)b * W * (2 * (size_t)n);
             const uint32_t mask = (1u << c) - 1u, half = 1u << (c - 1);
 #pragma unroll
             for (int e = 0; e < 2; e++) {
@@ -111,18 +114,18 @@ KERNEL void k_digits(const unsigned char *__restrict__ scalars, uint32_t n, uint
                 if (s.l[k]) len = 32u * k + (32u - (uint32_t)__builtin_clz(s.l[k]));
             atomicAdd(&bins[len > 255 ? 255 : len], 1u);
         }
-        int16_t *dg = digits + (size_t)b * W * n;
+        DIGIT *dg = digits + (size_t)b * W * n;
         const uint32_t mask = (1u << c) - 1u, half = 1u << (c - 1);
         uint32_t carry = 0;
         for (uint32_t w = 0; w < W; w++) {
             uint32_t raw = (s.l[0] & mask) + carry;
 #pragma unroll
-            for (int k = 0; k < 7; k++) s.l[k] = (s.l[k] >> c) | (s.l[k + 1] << (32 - c));   // c in [1,16]
+            for (int k = 0; k < 7; k++) s.l[k] = (s.l[k] >> c) | (s.l[k + 1] << (32 - c));   // c in [1,16] (int16), [1,20] (int32)
             s.l[7] >>= c;
             int32_t d;
             if (raw >= half) { d = (int32_t)raw - (int32_t)(1u << c); carry = 1; }
             else { d = (int32_t)raw; carry = 0; }
-            dg[(size_t)w * n + i] = (int16_t)d;
+            dg[(size_t)w * n + i] = (DIGIT)d;
         }
         }
     }
@@ -183,10 +186,14 @@ KERNEL void k_scan_a(const uint32_t *__restrict__ counts, uint32_t NB, uint32_t 
     }
     if (threadIdx.x == 0) block_sums[blockIdx.x] = red[0];
 }
-// one workgroup of 1024 lanes; nblocks <= 1024
+// one workgroup of 1024 lanes over the nblocks block sums: lane t takes ceil(nblocks / 1024) consecutive ones (one up to 1024
+// blocks, 2^21 counters; eight at the 2^24 counters of SCAN_MAX_COUNTERS) and carries its running total through them
 KERNEL void k_scan_b(uint32_t *__restrict__ block_sums, uint32_t nblocks) {
     __shared__ uint32_t buf[1024];
-    uint32_t v = threadIdx.x < nblocks ? block_sums[threadIdx.x] : 0;
+    const uint32_t per = (nblocks + 1023) / 1024, lo = threadIdx.x * per;
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < per; k++)
+        if (lo + k < nblocks) v += block_sums[lo + k];
     buf[threadIdx.x] = v;
     __syncthreads();
     for (uint32_t off = 1; off < 1024; off <<= 1) {
@@ -195,7 +202,9 @@ KERNEL void k_scan_b(uint32_t *__restrict__ block_sums, uint32_t nblocks) {
         buf[threadIdx.x] += add;
         __syncthreads();
     }
-    if (threadIdx.x < nblocks) block_sums[threadIdx.x] = buf[threadIdx.x] - v;   // exclusive
+    uint32_t run = buf[threadIdx.x] - v;                          // exclusive
+    for (uint32_t k = 0; k < per; k++)
+        if (lo + k < nblocks) { const uint32_t x = block_sums[lo + k]; block_sums[lo + k] = run; run += x; }
 }
 // offsets[NB] = total number of sorted entries; cursor = copy of offsets for k_scatter.
 // Optional by-products (null = skip), each of which used to be a launch of its own:

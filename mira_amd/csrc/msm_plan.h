@@ -6,9 +6,17 @@
 // the plan of one launch sequence over n scalars of `bits` bits (256, or GLV_BITS for the halves of the GLV split); forced_c != 0
 // names the width, else the measured cost model picks it -- from bitlen_hist (the bit lengths of the count * n scalars of the
 // previous commit of this shape) when given
-MsmPlan make_plan(size_t n, int32_t forced_c, uint32_t count = 1, uint64_t stride = 0, const uint32_t *bitlen_hist = nullptr, uint32_t bits = 256);
+// cmax (17 .. 20, plain path only): the key opted into wide windows (mira_msm_set_handle_max_window_bits); the model then takes
+// one where its measured table puts it at least 2 % ahead
+MsmPlan make_plan(size_t n, int32_t forced_c, uint32_t count = 1, uint64_t stride = 0, const uint32_t *bitlen_hist = nullptr, uint32_t bits = 256,
+                  uint32_t cmax = MSM_MAX_NARROW_C);
 // ... over one of a key's shared-bucket table sets
 MsmPlan make_plan_shared(size_t n, const Bases::SharedSet &set, uint64_t table_n, uint32_t count = 1, uint64_t stride = 0);
+// a batch of MSMs over n `bits`-bit scalars (n: the columns of one commitment's digit matrix): commitments per launch, and the plan of a
+// launch of cnt of them -- a planned width never puts more than SCAN_MAX_COUNTERS bucket counters into one launch (scan_width_cap)
+uint32_t scan_width_cap(uint32_t count, uint32_t bits, uint32_t cmax);
+size_t batch_per_launch(size_t n, int32_t forced_c, uint32_t bits, uint32_t cmax);
+MsmPlan make_batch_plan(size_t n, int32_t forced_c, uint32_t cnt, uint64_t stride, uint32_t bits, uint32_t cmax);
 // pieces per bucket set when at most max_points points may come back per commitment
 uint32_t default_pieces(const MsmPlan &p, uint32_t max_points);
 // the key's shared-bucket set for a commit of n pairs (count of them in one submission), or null when the key has none

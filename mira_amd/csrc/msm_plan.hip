@@ -9,7 +9,7 @@
 struct MeasuredWalls {
     int rows;
     int log_n[11];
-    double wall_us[11][17];
+    double wall_us[11][21];
     double interpolate(uint32_t c, double n) const {
         const double x = std::log2(std::max(n, 1.0));
         if (x <= log_n[0]) return wall_us[0][c];
@@ -149,6 +149,25 @@ static double plan_cost_us(uint32_t c, double n, uint32_t count, const double *b
     if (bitlen_hist) n_eff = dense_equivalent(c, bitlen_hist, plan_uniform_fractions(), 0, false, count, &heavy);
     return PLAN_WALLS.interpolate(c, n_eff * count) + heavy + W * (count - 1) * B / 5800.0;
 }
+// The wide windows of the plain path (17 .. 20 bits: int32 digits, the two-level front of msm_host.cuh) have a table of their own,
+// measured with 15 and 16 bits beside them in one process (tools/wide_window_probe.py, uniform scalars, one box:
+// profiles/r05_wide_windows.txt).  Only its RATIOS are used: make_plan scales the 16-bit wall of PLAN_WALLS by
+// WIDE(c) / WIDE(16), and takes a wide width where that puts it 2 % ahead of the narrow model's best -- as choose_glv does.
+static const MeasuredWalls WIDE_WALLS = {
+    5, {20, 22, 24, 26, 28},
+    {
+    //                                                    c = 15      16      17      18      19      20
+    {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,     1866,   1816,   1933,   2267,   2751,   4000},
+    {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,     6374,   6023,   6011,   6453,   6672,   7180},
+    {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,    23700,  22393,  22055,  22352,  21948,  21462},
+    {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,    92656,  86971,  85485,  85616,  82857,  78441},
+    {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,   376924, 354433, 344830, 343482, 327019, 305107},
+    }};
+static double wide_cost_us(uint32_t c, double n, uint32_t count, const double *bitlen_hist) {
+    double heavy = 0, n_eff = n;
+    if (bitlen_hist) n_eff = dense_equivalent(c, bitlen_hist, plan_uniform_fractions(), 0, false, count, &heavy);
+    return WIDE_WALLS.interpolate(c, n_eff * count) + heavy + std::ceil(256.0 / c) * (count - 1) * (double)(1u << (c - 1)) / 5800.0;
+}
 // n halves (2 x the pairs); with the bit lengths of the previous commit's halves: the dense commit with as many bucket additions,
 // plus what its heavy buckets cost beyond a uniform vector's
 static double glv_cost_us(uint32_t c, double n_halves, const double *hist, uint32_t count = 1) {
@@ -160,17 +179,25 @@ static double glv_cost_us(uint32_t c, double n_halves, const double *hist, uint3
     return GLV_WALLS.interpolate(c, pairs * count) + heavy + (double)W * (count - 1) * (double)(1u << (c - 1)) / 5800.0;
 }
 
-MsmPlan make_plan(size_t n, int32_t forced_c, uint32_t count, uint64_t stride, const uint32_t *bitlen_hist, uint32_t bits) {
+MsmPlan make_plan(size_t n, int32_t forced_c, uint32_t count, uint64_t stride, const uint32_t *bitlen_hist, uint32_t bits, uint32_t cmax) {
     MsmPlan p;
     uint32_t best_c = 13;
     double best = 1e300;
     double per_msm[256];
     if (bitlen_hist)
         for (int len = 0; len < 256; len++) per_msm[len] = (double)bitlen_hist[len] / count;
-    for (uint32_t c = (bits == 256 ? 4 : 5); c <= 16 && !forced_c; c++) {
+    for (uint32_t c = (bits == 256 ? 4 : 5); c <= std::min<uint32_t>(cmax, MSM_MAX_NARROW_C) && !forced_c; c++) {
         const double cost = bits == 256 ? plan_cost_us(c, (double)n, count, bitlen_hist ? per_msm : nullptr)
                                         : glv_cost_us(c, (double)n, bitlen_hist ? per_msm : nullptr, count);   // the halves of the GLV split: their own table
         if (cost < best * 0.99) { best = cost; best_c = c; }    // ties go to the narrower window (fewer buckets: less that skewed data can upset)
+    }
+    if (!forced_c && bits == 256 && cmax > MSM_MAX_NARROW_C) {     // a key that opted into wide windows: 17 .. cmax bits from their own table
+        const double *h = bitlen_hist ? per_msm : nullptr;
+        const double narrow16 = plan_cost_us(MSM_MAX_NARROW_C, (double)n, count, h), wide16 = wide_cost_us(MSM_MAX_NARROW_C, (double)n, count, h);
+        for (uint32_t c = MSM_MAX_NARROW_C + 1; c <= std::min<uint32_t>(cmax, MSM_MAX_C); c++) {
+            const double cost = narrow16 * wide_cost_us(c, (double)n, count, h) / wide16;
+            if (cost < best * 0.98) { best = cost; best_c = c; }
+        }
     }
     p.c = forced_c ? (uint32_t)forced_c : best_c;
     p.est_us = forced_c ? 0.0 : best;
@@ -192,6 +219,27 @@ MsmPlan make_plan(size_t n, int32_t forced_c, uint32_t count, uint64_t stride, c
     plan_reduction(p, 1);                                    // callers that can take several pieces per window ask again
     return p;
 }
+// Batches (capi.hip: msm_batch_device_locked).  The number of commitments per launch comes from the plan of ONE commitment; the
+// plan of a launch of cnt commitments is then made for cnt of them, and it may pick another width -- the model of a batch is the
+// commit of n cnt pairs, whose rows favour wider windows.  So that its counters still fit one scan, that plan's widths are capped at
+// the widest c with ceil(bits / c) cnt 2^(c-1) <= SCAN_MAX_COUNTERS (without the cap, a key that opted into wide windows planned
+// 3 x 2^23 pairs at 20 bits: 20.4 M counters, a launch the scan refuses).  A forced width is not capped: per_launch is sized by it.
+uint32_t scan_width_cap(uint32_t count, uint32_t bits, uint32_t cmax) {
+    uint32_t c = cmax;
+    while (c > 4 && (uint64_t)((bits + c - 1) / c) * count * (1ull << (c - 1)) > SCAN_MAX_COUNTERS) c--;
+    return c;
+}
+size_t batch_per_launch(size_t n, int32_t forced_c, uint32_t bits, uint32_t cmax) {
+    const MsmPlan p1 = make_plan(n, forced_c, 1, 0, nullptr, bits, cmax);
+    // W_total * B counters within the scan's capacity and n * W_total entries < 2^32 (a configuration beyond the capacity, one
+    // commitment per launch, is refused by the launch sequence)
+    return std::max<size_t>(1, std::min<size_t>((size_t)(SCAN_MAX_COUNTERS / ((uint64_t)p1.W * p1.B)),
+                                                 (size_t)(((1ull << 32) - 1) / ((uint64_t)std::max<size_t>(n, 1) * p1.W))));
+}
+MsmPlan make_batch_plan(size_t n, int32_t forced_c, uint32_t cnt, uint64_t stride, uint32_t bits, uint32_t cmax) {
+    return make_plan(n, forced_c, cnt, stride, nullptr, bits, forced_c ? cmax : scan_width_cap(cnt, bits, cmax));
+}
+
 // Pieces per bucket set for a commit whose points the library's own epilogue combines (host_curve.hpp: horner_pieces): the device's
 // Horner chain over the bits of a bucket index is cut into P parts and the host's chain of doublings, which passes every bit
 // position anyway, adds P points per window instead of one (0.25 us each).
@@ -290,12 +338,12 @@ const Bases::SharedSet *trial_set(const Bases &bs, const Bases::WidthTrial &t, c
     for (const auto &set : bs.shared) if (set.c == c) return &set;
     return model;
 }
-// candidate k after the model's choice, 0 where there is none: a neighbour width (TRIAL_OFFSETS) within 4 .. 16 (the halves of
-// the GLV split from 5), or the key's k-th set unless it is the model's (that one went first)
+// candidate k after the model's choice, 0 where there is none: a neighbour width (TRIAL_OFFSETS) within 4 .. 16 -- up to the key's
+// mira_msm_set_handle_max_window_bits on the plain path -- (the halves of the GLV split from 5), or the key's k-th set unless it is the model's (that one went first)
 static uint32_t trial_candidate(const Bases::WidthTrial &t, const Bases &bs, size_t k) {
     if (t.kind & 4) return bs.shared[k].c != t.c0 ? bs.shared[k].c : 0;
     const int c = (int)t.c0 + TRIAL_OFFSETS[k + 1];
-    return c >= ((t.kind & 1) ? 5 : 4) && c <= 16 ? (uint32_t)c : 0;
+    return c >= ((t.kind & 1) ? 5 : 4) && c <= (int)((t.kind & 1) ? MSM_MAX_NARROW_C : bs.max_c) ? (uint32_t)c : 0;   // (wide widths: keys that opted in, plain path)
 }
 void trial_report(Bases::WidthTrial &t, double us, const Bases &bs) {
     if (t.done) return;

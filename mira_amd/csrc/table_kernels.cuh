@@ -88,11 +88,14 @@ KERNEL void k_digits32(const unsigned char *__restrict__ scalars, uint32_t n, ui
     }
 }
 
-// coarse-bin histogram over the digits: grid = (ntiles, TABLE_W); LDS = TABLE_CB counters
-KERNEL void k_thist_coarse(const int32_t *__restrict__ digits, uint32_t n, uint32_t tile, uint32_t TABLE_FINE_BITS, uint32_t *__restrict__ counts) {
+// coarse-bin histogram over the digits: grid = (ntiles, windows); LDS = CB <= TABLE_CB counters.  Window w counts into
+// counts[w * set_stride + bin]: set_stride = 0, one set for all windows (table mode); CB, a set per window (the two-level front
+// of the per-window path, msm_host.cuh)
+KERNEL void k_thist_coarse(const int32_t *__restrict__ digits, uint32_t n, uint32_t tile, uint32_t TABLE_FINE_BITS, uint32_t *__restrict__ counts,
+                           uint32_t CB, uint32_t set_stride) {
     __shared__ uint32_t bins[TABLE_CB];
     const uint32_t w = blockIdx.y;
-    for (uint32_t b = threadIdx.x; b < TABLE_CB; b += blockDim.x) bins[b] = 0;
+    for (uint32_t b = threadIdx.x; b < CB; b += blockDim.x) bins[b] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * tile, end = (base + tile < n) ? base + tile : n;
     const int32_t *dw = digits + (size_t)w * n;
@@ -101,8 +104,9 @@ KERNEL void k_thist_coarse(const int32_t *__restrict__ digits, uint32_t n, uint3
         if (d != 0) atomicAdd(&bins[((uint32_t)(d < 0 ? -d : d) - 1) >> TABLE_FINE_BITS], 1u);
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < TABLE_CB; b += blockDim.x) {
+    uint32_t *cw = counts + (size_t)w * set_stride;
+    for (uint32_t b = threadIdx.x; b < CB; b += blockDim.x) {
         uint32_t cnt = bins[b];
-        if (cnt) atomicAdd(&counts[b], cnt);
+        if (cnt) atomicAdd(&cw[b], cnt);
     }
 }
