@@ -219,6 +219,12 @@ int mira_msm_last_table_bits(int32_t *table_bits);
  * by the top 9 bits of the bucket, bucket counts from that output; csrc/msm_host.cuh); default 17, the first width whose bucket
  * histogram does not fit LDS.  Tests set it low so that narrow widths run through that front at sizes the CPU emulation reaches */
 #define MIRA_TUNE_WIDE_FRONT_MIN_C 20
+/* mira_lookup_m_device: 1 = every key starts probing its hash table at slot 0 (tests: long probe chains at small sizes);
+ * default / 0 = hashed.  Never changes a result */
+#define MIRA_TUNE_LOOKUP_HASH 21
+/* elements per lane of every level of a batch inversion (mira_batch_invert_device, mira_lookup_h_g_device), 2 .. 64, default 8.
+ * Never changes a result */
+#define MIRA_TUNE_INV_CHUNK 22
 int mira_set_tuning(int knob, int64_t value);
 
 /* Read a range of the registered key back in the reference layout (cache file writing,
@@ -252,6 +258,23 @@ int mira_g1_lincomb(int curve, const uint64_t acc[8], const uint64_t *scalars /*
  * region on the host threads (every W commitment and every group of cross-term commitments is a task). */
 int mira_g1_fold_commitments(int curve, const uint64_t r[4], const uint64_t *w1 /* nw * 8 */, const uint64_t *w2 /* nw * 8 */, size_t nw,
                              const uint64_t e[8], const uint64_t *t_commits /* count * 8 */, size_t count, uint64_t *w_out /* nw * 8 */, uint64_t e_out[8]);
+
+/* ---- the lookup argument's witness rounds (src/plonk/lookup.rs:278-321) --------------------------
+ * Vectors of 32-byte Montgomery elements in HBM, field MIRA_FIELD_FQ / MIRA_FIELD_FR.  n = 0 is a no-op.  A null pointer with
+ * n > 0, an unknown field, or an output overlapping an input (other than in-place inversion) -> MIRA_E_BAD_ARG; a length of 2^32
+ * or more -> MIRA_E_UNSUPPORTED; a workspace that does not fit -> MIRA_E_ALLOC.  An input element >= the modulus (equality is
+ * decided on the representation) -> MIRA_E_BAD_ARG, the outputs are then unspecified.  Results do not depend on scheduling.
+ *
+ * mira_batch_invert_device: out[i] = in[i]^-1, 0 -> 0; d_out == d_in allowed.  The per-element `invert()` of evaluate_h_g
+ * (lookup.rs:309-321), by Montgomery's trick: one Fermat inversion per call.
+ * mira_lookup_m_device: evaluate_m (lookup.rs:278-307): m[i] = F::from_u128(#{j : l[j] == t[i]}) if t[i] is the first
+ * occurrence of its value in t, else 0 (an l value absent from t counts nowhere).  Replaces the HashMap / HashSet pass.
+ * mira_lookup_h_g_device: evaluate_h_g (lookup.rs:309-321): h[i] = 1 / (l[i] + r), g[i] = m[i] / (t[i] + r), 0 where the
+ * denominator is 0; both vectors share one batch inversion.  r: Montgomery form, canonical. */
+int mira_batch_invert_device(int field, void *d_out, const void *d_in, size_t n);
+int mira_lookup_m_device(int field, void *d_m /* n_t */, const void *d_l, size_t n_l, const void *d_t, size_t n_t);
+int mira_lookup_h_g_device(int field, void *d_h /* n_l */, void *d_g /* n_t */, const void *d_l, size_t n_l,
+                           const void *d_t, const void *d_m, size_t n_t, const uint64_t r[4] /* Montgomery */);
 
 /* ---- the step before the MSM in one fold: cross-term evaluation ----------------------------
  * GraphEvaluator::evaluate over all rows (src/polynomial/graph_evaluator.rs:361-390, called per

@@ -561,7 +561,7 @@ int mira_msm_combine(int curve, const uint64_t *partials, size_t nparts, int32_t
 }
 int mira_set_tuning(int knob, int64_t value) {
     std::lock_guard<std::mutex> lk(g_lock);
-    if (knob < 0 || knob > MIRA_TUNE_WIDE_FRONT_MIN_C || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
+    if (knob < 0 || knob > MIRA_TUNE_INV_CHUNK || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
     g.tune[knob] = value;
     return MIRA_OK;
 }
@@ -682,7 +682,8 @@ int mira_trim(size_t keep_bytes, size_t *released_out) {
     // `consts`, `ntt_consts` and `fold_consts` hold uploaded constants (a few hundred bytes): never released
     std::vector<DevBuf *> bufs = {&g.digits, &g.counts, &g.offsets, &g.cursor, &g.block_sums, &g.sorted_idx, &g.bucket_sums, &g.part, &g.coarse_offsets,
                                   &g.fine_counts, &g.fine_cursor, &g.head_part, &g.tail_part, &g.tail_key, &g.heavy, &g.heavy_out, &g.chunks, &g.window_sums,
-                                  &g.scalars_stage, &g.ntt_tmp, &g.ntt_stage, &g.graph_ws, &g.tree_a, &g.tree_b, &g.hist_dev};
+                                  &g.scalars_stage, &g.ntt_tmp, &g.ntt_stage, &g.graph_ws, &g.tree_a, &g.tree_b, &g.hist_dev,
+                                  &g.inv_ws, &g.lk_owner, &g.lk_first, &g.lk_count, &g.lk_slot};
     for (int i = 0; i < Ctx::NTT_SETS; i++) bufs.push_back(&g.ntt_set[i]);
     size_t total = 0;
     for (DevBuf *b : bufs) total += b->cap;
@@ -764,6 +765,60 @@ int mira_fold_relaxed_witness_device(int field, void *d_w_out, const void *d_w1,
         if (n && !d_cross_terms[k]) { set_error("null cross term"); return MIRA_E_BAD_ARG; }
     if (!n_w && !n) return MIRA_OK;
     return fold_relaxed_device(field, d_w_out, d_w1, d_w2, n_w, d_e_out, d_e, d_cross_terms, num_terms, r, n);
+}
+// ---- lookup argument (lookup.hip)
+static bool lk_field_ok(int field) { return field == MIRA_FIELD_FQ || field == MIRA_FIELD_FR; }
+// [a, a + 32 na) and [b, b + 32 nb) share a byte
+static bool lk_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + 32 * nb && y < x + 32 * na;
+}
+static int lk_check_len(size_t n) {
+    if ((uint64_t)n >= (1ull << 32)) { set_error("lookup vectors of 2^32 elements or more are not supported"); return MIRA_E_UNSUPPORTED; }
+    return MIRA_OK;
+}
+int mira_batch_invert_device(int field, void *d_out, const void *d_in, size_t n) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!lk_field_ok(field) || (n && (!d_out || !d_in))) { set_error("bad batch-inversion arguments"); return MIRA_E_BAD_ARG; }
+    if (!n) return MIRA_OK;
+    if ((rc = lk_check_len(n))) return rc;
+    if (d_out != d_in && lk_overlap(d_out, n, d_in, n)) { set_error("the output overlaps the input (only d_out == d_in is allowed)"); return MIRA_E_BAD_ARG; }
+    return batch_invert_device(field, d_out, d_in, n);
+}
+int mira_lookup_m_device(int field, void *d_m, const void *d_l, size_t n_l, const void *d_t, size_t n_t) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!lk_field_ok(field) || (n_t && (!d_m || !d_t)) || (n_l && n_t && !d_l)) { set_error("bad lookup_m arguments"); return MIRA_E_BAD_ARG; }
+    if (!n_t) return MIRA_OK;
+    if ((rc = lk_check_len(n_l)) || (rc = lk_check_len(n_t))) return rc;
+    if (lk_overlap(d_m, n_t, d_t, n_t) || lk_overlap(d_m, n_t, d_l, n_l)) { set_error("m overlaps an input"); return MIRA_E_BAD_ARG; }
+    return lookup_m_device(field, d_m, d_l, n_l, d_t, n_t);
+}
+int mira_lookup_h_g_device(int field, void *d_h, void *d_g, const void *d_l, size_t n_l, const void *d_t, const void *d_m, size_t n_t, const uint64_t r[4]) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!lk_field_ok(field) || !r || (n_l && (!d_h || !d_l)) || (n_t && (!d_g || !d_t || !d_m))) { set_error("bad lookup_h_g arguments"); return MIRA_E_BAD_ARG; }
+    if (!n_l && !n_t) return MIRA_OK;
+    if ((rc = lk_check_len(n_l)) || (rc = lk_check_len(n_t))) return rc;
+    const void *ins[3] = {d_l, d_t, d_m};
+    const size_t in_n[3] = {n_l, n_t, n_t};
+    for (int k = 0; k < 3; k++)
+        if (lk_overlap(d_h, n_l, ins[k], in_n[k]) || lk_overlap(d_g, n_t, ins[k], in_n[k])) { set_error("an output of lookup_h_g overlaps an input"); return MIRA_E_BAD_ARG; }
+    if (lk_overlap(d_h, n_l, d_g, n_t)) { set_error("h and g overlap"); return MIRA_E_BAD_ARG; }
+    // r is compared on its representation like the vectors: it must be below the modulus
+    uint32_t rw[8];
+    memcpy(rw, r, 32);
+    const uint32_t *P = field == MIRA_FIELD_FR ? FrP::P : FqP::P;
+    bool below = false;
+    for (int k = 7; k >= 0; k--)
+        if (rw[k] != P[k]) { below = rw[k] < P[k]; break; }
+    if (!below) { set_error("r is not canonical (>= the modulus)"); return MIRA_E_BAD_ARG; }
+    return lookup_h_g_device(field, d_h, d_g, d_l, n_l, d_t, d_m, n_t, r);
 }
 int mira_lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint64_t *coeffs, size_t num_vecs, size_t n) {
     std::lock_guard<std::mutex> lk(g_lock);

@@ -129,6 +129,8 @@ struct Ctx {
     DevBuf graph_consts, graph_ws;
     DevBuf hist_dev;
     DevBuf tree_w, tree_a, tree_b;   // weighted tree reduction: level weights, ping-pong partial results
+    DevBuf inv_ws;                   // batch inversion: upper levels' values and prefix products (lookup.hip)
+    DevBuf lk_owner, lk_first, lk_count, lk_slot, lk_err;   // the multiplicities' hash table, every t element's slot, the error word
     uint32_t hist_host[256] = {};    // the statistics of the last commit that collected them
     int32_t last_c = 0, last_w = 0;  // mira_msm_last_plan
     int32_t last_table_c = 0;        // mira_msm_last_table_bits: width of the table set the last commit went through, 0 = none
@@ -296,6 +298,11 @@ int fold_relaxed_device(int field, void *d_w_out, const void *d_w1, const void *
 int lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint64_t *coeffs, size_t K, size_t n);
 int lincomb_multi_device(int field, void *const *d_outs, size_t M, const void *const *d_vecs, size_t J, const uint64_t *coeffs, size_t n);
 int pow_tree_reduce_device(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out);
+
+// lookup.hip
+int batch_invert_device(int field, void *d_out, const void *d_in, size_t n);
+int lookup_m_device(int field, void *d_m, const void *d_l, size_t n_l, const void *d_t, size_t n_t);
+int lookup_h_g_device(int field, void *d_h, void *d_g, const void *d_l, size_t n_l, const void *d_t, const void *d_m, size_t n_t, const uint64_t r[4]);
 
 // graph.hip
 int graph_compile(int field, const mira_graph *gr, uint32_t num_challenges, uint32_t num_columns, uint64_t *handle_out);

@@ -46,6 +46,49 @@ template <int K> static __device__ __forceinline__ uint32_t quad_bcast(uint32_t 
 // a word of mapped host memory the host spins on (ctx.h: rt_wait_flag)
 static __device__ __forceinline__ void store_release_system(uint64_t *p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 #define DYN_SHARED(type, name) extern __shared__ __attribute__((aligned(16))) unsigned char name##_raw[]; type *name = reinterpret_cast<type *>(name##_raw)
+// Global-memory atomics of the hash table in lookup_kernels.cuh (vector-memory atomics: plain HIP builtins)
+static __device__ __forceinline__ uint64_t atomic_cas_u64(uint64_t *p, uint64_t cmp, uint64_t val) {
+    return (uint64_t)atomicCAS(reinterpret_cast<unsigned long long *>(p), (unsigned long long)cmp, (unsigned long long)val);
+}
+static __device__ __forceinline__ uint32_t atomic_min_u32(uint32_t *p, uint32_t v) { return atomicMin(p, v); }
+// Wave-level aggregation before an atomic on a hot address: among the active lanes of the calling wave, those whose `key`
+// equals this lane's form a group; *count = its size, and the return value is true for its lowest lane only (the one that
+// issues the group's atomic).  Every pass of the loop retires the group of the lowest remaining lane, so it ends after at
+// most 64 passes; no lane waits for another.
+static __device__ __forceinline__ bool wave_group_leader(uint64_t key, uint32_t *count, uint32_t *leader_lane = nullptr) {
+    uint64_t todo = __ballot(1);
+    const uint32_t lane = __lane_id();
+    for (;;) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint64_t lk = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), leader) << 32) |
+                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, leader);
+        const uint64_t same = __ballot(key == lk);
+        if (key == lk) {
+            *count = (uint32_t)__popcll(same);
+            if (leader_lane) *leader_lane = (uint32_t)leader;
+            return lane == (uint32_t)leader;
+        }
+        todo &= ~same;
+    }
+}
+// v of lane `src` of the calling wave (which must be active)
+static __device__ __forceinline__ uint64_t wave_shfl_u64(uint64_t v, uint32_t src) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src);
+    return ((uint64_t)hi << 32) | lo;
+}
 #else
 #include "../../tests/emu/emu.h"
+// lookup_kernels.cuh: emulated lanes are not in lockstep, so there is no wave to aggregate over; every lane issues its own atomic
+// (the values are the same: the atomics are additions and minima)
+inline uint64_t atomic_cas_u64(uint64_t *p, uint64_t cmp, uint64_t val) {
+    __atomic_compare_exchange_n(p, &cmp, val, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return cmp;
+}
+inline uint32_t atomic_min_u32(uint32_t *p, uint32_t v) {
+    uint32_t o = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < o && !__atomic_compare_exchange_n(p, &o, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return o;
+}
+inline bool wave_group_leader(uint64_t, uint32_t *count, uint32_t *leader_lane = nullptr) { *count = 1; if (leader_lane) *leader_lane = 0; return true; }
+inline uint64_t wave_shfl_u64(uint64_t v, uint32_t) { return v; }   // every emulated lane leads its own group: it only ever reads itself
 #endif
