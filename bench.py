@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: BN256 G1 MSM throughput through CommitmentKey::commit on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one MSM (the whole commit hot path: digit recoding, bucket sort, bucket accumulation,
 bucket reduction, window combine, to_affine) over one batch of synthetic scalars, with scalars and
@@ -11,10 +11,15 @@ GPU (weak scaling); each rank reduces its chunk to W window sums, one RCCL all-g
 them (W * 128 bytes per rank) and every rank combines -- EC addition is not an RCCL reduction
 operator, so all-gather + local add is the exchange.
 
-Prints ONE JSON line on rank 0.  Extra keys: `roofline` (dominant kernel k_accumulate, algorithmic
-bytes = 96 B per pair), `cpu_baseline` (the C restatement of the reference's
-best_multiexp on the host cores, bounded sample), `stages_ms`, and at N = 1 `extras` with the
-2^24 NTT and the k = 17 fold-step MSM schedule beside their CPU timings.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set up, W warm-up
+steps, K timed steps, --dump-outputs, the line.  Besides the headline keys the line carries what
+the timed steps themselves measured: `stages_ms`, `roofline` (dominant kernel k_accumulate,
+algorithmic bytes = 96 B per pair) and the result point.  --full also runs, after
+the timed steps, everything that takes runs of its own: `cpu_baseline` and `parity` (the C
+restatement of the reference's best_multiexp on the host cores, bounded sample), at N = 1 `extras`
+(the 2^24 NTT, other MSM sizes and modes, the k = 17 fold-step chain and more, beside their CPU
+timings) with `secondary_metric`, and at N > 1 the scaling `extras`.  --no-cpu, --no-extras and
+--no-key-load trim a --full run.
 """
 import argparse
 import ctypes
@@ -87,9 +92,11 @@ def main():
     ap.add_argument("--total-log-n", type=int, default=0,
                     help="strong scaling (BASELINE configs[4]): one MSM of 2^N pairs cut into --gpus point chunks (default 26 at --gpus > 1)")
     ap.add_argument("--window-bits", type=int, default=16)
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-key-load", action="store_true", help="skip the 8 GiB commitment-key file leg of the extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baseline, the parity check and the extras (other sizes, modes and workloads)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline, the parity check and the CPU legs of the extras")
+    ap.add_argument("--no-key-load", action="store_true", help="with --full: skip the 8 GiB commitment-key file leg of the extras")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="REHEARSAL ONLY: all ranks share GPU 0 and exchange over gloo -- the whole multi-rank path with the product library on a one-GPU box; never a measurement")
     ap.add_argument("--emulate", action="store_true",
@@ -99,6 +106,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    with_extras = args.full and not args.no_extras         # a plain run: the headline alone
+    with_cpu = args.full and not args.no_cpu
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -266,13 +275,13 @@ def main():
         out["ranks"] = gathered
         out["agreed_window"] = {"window_bits": mine["window_bits"], "num_windows": mine["num_windows"],
                                 "same_on_all_ranks": len({(g_["window_bits"], g_["num_windows"]) for g_ in gathered}) == 1}
-    if strong and n_gpus > 1 and dist is not None and not args.emulate and not args.no_extras:
+    if strong and n_gpus > 1 and dist is not None and not args.emulate and with_extras:
         out["extras"] = multi_gpu_extras(lib, cm, dist, rank, n_gpus, total_log_n, args)
-    if rank == 0 and n_gpus == 1 and not args.no_cpu:
+    if rank == 0 and n_gpus == 1 and with_cpu:
         out["cpu_baseline"], parity = cpu_baseline_msm(lib, cm, key, d_scalars, n, window_bits)
         out["parity"] = parity
-    if rank == 0 and n_gpus == 1 and not args.no_extras:
-        out["extras"] = extras(lib, cm, not args.no_cpu, args.no_key_load)
+    if rank == 0 and n_gpus == 1 and with_extras:
+        out["extras"] = extras(lib, cm, with_cpu, args.no_key_load)
         # BASELINE.json's metric names two figures: the MSM throughput above and "NIFS fold-step ms (k=17)" (configs[3]).  The
         # second one is measured in the same run (extras.nifs_fold_step_k17 has the spans and the variants) and repeated here, at
         # the top level of the line, beside the CPU port's time for the same chain on this box's host cores.

@@ -34,3 +34,14 @@ def test_bench_gpus2_launches_two_ranks(emu_lib):
 def test_bench_gpus2_weak_variant(emu_lib):
     out = run_bench("--gpus", "2", "--emulate", "--log-n", "7", "--window-bits", "8", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["total_pairs"] == 256
+
+
+def test_bench_plain_run_is_the_headline_alone(emu_lib):
+    """Without --full the line holds the headline and what the timed steps measured, nothing that takes runs of its own."""
+    from oracle import cref as C
+    out = run_bench("--gpus", "1", "--emulate", "--log-n", "7", "--window-bits", "8", "--steps", "1", "--warmup", "1")
+    assert out["n_gpus"] == 1 and out["steps"] == 1 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert not {"cpu_baseline", "parity", "extras", "secondary_metric"} & set(out)
+    n = 1 << 7
+    want = C.msm_pippenger(0, C.synth_scalars(0, n), C.synth_bases(0, n))
+    assert [int(v, 16) for v in out["result_affine_u64"]] == [int(v) for v in want]

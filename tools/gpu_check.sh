@@ -1,13 +1,17 @@
 #!/bin/bash
-# Development helper for one gpurun call: GPU parity tests, then the headline bench.
-# usage: tools/gpu_check.sh <tag> [bench args]
+# Development helper: GPU parity tests, then the full bench line (headline, CPU baseline, extras).
+# usage: OUT_DIR=<results directory> tools/gpu_check.sh <tag> [bench args]
 tag=${1:-x}; shift
-mkdir -p gpurun_out
-timeout -k 10 500 python -m pytest tests -m gpu -x -q > gpurun_out/pytest_$tag.txt 2>&1; echo "pytest rc=$?"; tail -3 gpurun_out/pytest_$tag.txt
-timeout -k 10 500 python bench.py --steps 5 --warmup 2 "$@" > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err; echo "bench rc=$?"
+out=${OUT_DIR:?set OUT_DIR to the directory that receives the results}
+mkdir -p "$out"
+# a failed, faulted or timed-out step starts nothing further on the GPU
+timeout -k 10 500 python -m pytest tests -m gpu -x -q > "$out/pytest_$tag.txt" 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 "$out/pytest_$tag.txt"
+[ $rc -eq 0 ] || exit $rc
+timeout -k 10 600 python bench.py --steps 5 --warmup 2 --full "$@" > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"; rc=$?; echo "bench rc=$rc"
+[ $rc -eq 0 ] || exit $rc
 python - <<PY
 import json
-d=json.load(open("gpurun_out/bench_$tag.json"))
+d=json.load(open("$out/bench_$tag.json"))
 print("value", d["value"], d["unit"], "ms/step", d["ms_per_step"])
 print("stages", d["stages_ms"])
 print("roofline", d["roofline"]["achieved"], d["roofline"]["frac"])

@@ -9,7 +9,7 @@
 #      gpurun merges gpurun_out/ back, profiles/ is written in this container)
 # Steps are joined with && -- a failed or killed GPU step starts no further one.
 # A gpurun call is at most 20 minutes: part a = steps 1-3 and the MSM counters, part b = the NTT counters and the
-# full default bench line.
+# full bench line (bench.py --full).
 # usage: tools/gpu_profile_all.sh <tag> <a|b> [skip-tests]
 tag=${1:-x}
 part=${2:-a}
@@ -20,7 +20,7 @@ B="python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu"
 N="python3 tools/ntt_probe.py 24"
 if [ "$part" = "b" ]; then
   bash tools/gpu_pmc_ntt2.sh $tag > $out/pmcntt_$tag.txt 2>&1 && echo "ntt pmc ok" &&
-  timeout -k 10 600 python3 bench.py > $out/bench_full_$tag.json 2> $out/bench_full_$tag.err && echo "full bench ok"
+  timeout -k 10 600 python3 bench.py --full > $out/bench_full_$tag.json 2> $out/bench_full_$tag.err && echo "full bench ok"
   exit $?
 fi
 { [ -n "$3" ] || { timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $out/pytest_$tag.txt 2>&1; rc=$?; tail -3 $out/pytest_$tag.txt; [ $rc -eq 0 ]; }; } &&
