@@ -17,6 +17,31 @@ thread_local dim3 threadIdx, blockIdx;
 dim3 blockDim, gridDim;
 pthread_barrier_t *emu_barrier = nullptr;
 unsigned char *emu_dyn_shared = nullptr;
+#ifdef F29_TRACK
+// The branch census (f29_census.h), for the tests alone: not in include/mira_gpu.h.  One line per (kernel, section, function, exit),
+// "kernel|section|function|exit|count\n"; returns the length of the whole text, of which at most cap - 1 bytes and a terminating
+// zero are written to buf.
+extern "C" size_t mira_emu_census_read(char *buf, size_t cap) {
+    std::map<std::string, uint64_t> merged;
+    {
+        std::lock_guard<std::mutex> lk(emu_census.m);
+        for (const auto &kv : emu_census.hits)
+            merged[std::string(std::get<0>(kv.first)) + "|" + std::get<1>(kv.first) + "|" + std::get<2>(kv.first) + "|" + std::get<3>(kv.first)] += kv.second;
+    }
+    std::string text;
+    for (const auto &kv : merged) text += kv.first + "|" + std::to_string(kv.second) + "\n";
+    if (buf && cap) {
+        const size_t len = text.size() < cap - 1 ? text.size() : cap - 1;
+        memcpy(buf, text.data(), len);
+        buf[len] = 0;
+    }
+    return text.size();
+}
+extern "C" void mira_emu_census_reset() {
+    std::lock_guard<std::mutex> lk(emu_census.m);
+    emu_census.hits.clear();
+}
+#endif
 #endif
 
 static thread_local std::string g_err;

@@ -44,7 +44,8 @@ template <class F> HD Xyzz29<F> xyzz29_double_affine(const Aff29<F> &p) {
 }
 // 2 * XYZZ: dbl-2008-s-1
 template <class F> HD Xyzz29<F> xyzz29_double(const Xyzz29<F> &p) {
-    if (xyzz29_is_identity(p)) return p;
+    if (xyzz29_is_identity(p)) { F29_HIT("double", "identity_in"); return p; }
+    F29_HIT("double", "common");
     Xyzz29<F> r;
     Fe29<F> u = f29_dbl(p.y);                                   // < 10
     Fe29<F> v = f29_sqr(u);                                     // 100 <= 168
@@ -59,8 +60,9 @@ template <class F> HD Xyzz29<F> xyzz29_double(const Xyzz29<F> &p) {
 
 // acc += q (q affine, canonical): madd-2008-s, 8M + 2S on the common path
 template <class F> HD void xyzz29_add_affine(Xyzz29<F> &acc, const Aff29<F> &q) {
-    if (aff29_is_identity(q)) return;
+    if (aff29_is_identity(q)) { F29_HIT("add_affine", "identity_in"); return; }
     if (xyzz29_is_identity(acc)) {
+        F29_HIT("add_affine", "identity_in");
         acc.x = q.x; acc.y = q.y; acc.zz = f29_one<F>(); acc.zzz = f29_one<F>();
         return;
     }
@@ -69,10 +71,11 @@ template <class F> HD void xyzz29_add_affine(Xyzz29<F> &acc, const Aff29<F> &q) 
     Fe29<F> p = f29_sub<10>(u2, acc.x);                         // X1 < 9  -> P < 12
     Fe29<F> r = f29_sub<6>(s2, acc.y);                          // Y1 < 5  -> R < 8
     if (f29_is_zero_mod_p<12>(p)) {
-        if (f29_is_zero_mod_p<8>(r)) acc = xyzz29_double_affine(q);   // same point
-        else acc = xyzz29_identity<F>();                            // opposite points
+        if (f29_is_zero_mod_p<8>(r)) { F29_HIT("add_affine", "same"); acc = xyzz29_double_affine(q); }             // same point
+        else { F29_HIT("add_affine", "opposite"); acc = xyzz29_identity<F>(); }                                  // opposite points
         return;
     }
+    F29_HIT("add_affine", "common");
     Fe29<F> pp = f29_sqr(p);                                    // 144 <= 168
     Fe29<F> ppp = f29_mul(p, pp);                               // 24
     Fe29<F> qq = f29_mul(acc.x, pp);                            // 18
@@ -90,8 +93,8 @@ template <class F> HD void xyzz29_add_affine(Xyzz29<F> &acc, const Aff29<F> &q) 
 
 // acc += q (both XYZZ): add-2008-s, 12M + 2S
 template <class F> HD void xyzz29_add(Xyzz29<F> &acc, const Xyzz29<F> &q) {
-    if (xyzz29_is_identity(q)) return;
-    if (xyzz29_is_identity(acc)) { acc = q; return; }
+    if (xyzz29_is_identity(q)) { F29_HIT("add", "identity_in"); return; }
+    if (xyzz29_is_identity(acc)) { F29_HIT("add", "identity_in"); acc = q; return; }
     Fe29<F> u1 = f29_mul(acc.x, q.zz);                          // 18
     Fe29<F> u2 = f29_mul(q.x, acc.zz);
     Fe29<F> s1 = f29_mul(acc.y, q.zzz);                         // 10
@@ -99,10 +102,11 @@ template <class F> HD void xyzz29_add(Xyzz29<F> &acc, const Xyzz29<F> &q) {
     Fe29<F> p = f29_sub<3>(u2, u1);                             // < 5
     Fe29<F> r = f29_sub<3>(s2, s1);                             // < 5
     if (f29_is_zero_mod_p<5>(p)) {
-        if (f29_is_zero_mod_p<5>(r)) acc = xyzz29_double(acc);
-        else acc = xyzz29_identity<F>();
+        if (f29_is_zero_mod_p<5>(r)) { F29_HIT("add", "same"); acc = xyzz29_double(acc); }
+        else { F29_HIT("add", "opposite"); acc = xyzz29_identity<F>(); }
         return;
     }
+    F29_HIT("add", "common");
     Fe29<F> pp = f29_sqr(p);
     Fe29<F> ppp = f29_mul(p, pp);
     Fe29<F> qq = f29_mul(u1, pp);

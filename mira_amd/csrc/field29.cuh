@@ -42,15 +42,22 @@ static constexpr uint32_t M29 = 0x1FFFFFFFu;
 // subtraction bias fails deterministically instead of for one input in 2^60.
 #ifdef F29_TRACK
 #include <cassert>
+#include "f29_census.h"
 #define F29_BD(x) double bd = (x);
 #define F29_SET(v, x) ((v).bd = (x))
 #define F29_GET(v) ((v).bd)
 #define F29_ASSERT(c) assert(c)
+// branch census of the group law (curve29.cuh, quad29.cuh): which exit of which function ran, counted per kernel and per
+// section of a kernel by the emulation's launch macros (tests/emu/emu.h); read by tests/test_exceptional_points_emu.py
+#define F29_HIT(fn, site) emu_hit(fn, site)
+#define F29_REGION(name) EMU_REGION_SCOPE(name)           // until the end of the enclosing block
 #else
 #define F29_BD(x)
 #define F29_SET(v, x) ((void)0)
 #define F29_GET(v) (0.0)
 #define F29_ASSERT(c) ((void)0)
+#define F29_HIT(fn, site) ((void)0)
+#define F29_REGION(name) ((void)0)
 #endif
 static constexpr double F29_RP_OVER_P = 168.0;   // 2^261 / P = 168.9...: a*b <= 168 P^2 -> product < 2 P
 

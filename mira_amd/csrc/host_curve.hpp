@@ -93,6 +93,7 @@ static void host_parallel_for(size_t count, const std::function<void(size_t)> &f
 template <class FB>
 static void horner_pieces(const uint64_t *pts, const PartialShape &sh, uint64_t out[8]) {
     using namespace hostf;
+    HOSTF_REGION("horner_pieces");
     HXyzz<FB> acc = identity<FB>();
     uint32_t at = 0;                                         // bit position the accumulator currently stands at
     bool first = true;
@@ -111,6 +112,7 @@ static void horner_pieces(const uint64_t *pts, const PartialShape &sh, uint64_t 
 template <class FB>
 static void sum_partials(const uint64_t *partials, size_t nparts, uint32_t W, uint64_t *out_windows) {
     using namespace hostf;
+    HOSTF_REGION("sum_partials");
     for (uint32_t w = 0; w < W; w++) {
         HXyzz<FB> acc = identity<FB>();
         for (size_t k = 0; k < nparts; k++) {
@@ -172,6 +174,7 @@ template <class FB> struct OddMultiples {                        // (2 i + 1) P,
 // sum_i k_i P_i, one shared chain of doublings (Straus over the NAFs); scalars in Montgomery form, points affine
 template <class FB, class FS> static hostf::HXyzz<FB> g1_straus(const uint64_t *scalars, const uint64_t *points, size_t count) {
     using namespace hostf;
+    HOSTF_REGION("g1");
     std::vector<Wnaf5> naf;
     std::vector<OddMultiples<FB>> table;
     naf.reserve(count); table.reserve(count);
@@ -196,6 +199,7 @@ template <class FB, class FS> static hostf::HXyzz<FB> g1_straus(const uint64_t *
 // acc + scalar * point on affine points: the single-scalar best_multiexp calls of
 // RelaxedPlonkInstance::fold (src/plonk/mod.rs:986-999, 1049-1053).
 template <class FB, class FS> static void g1_mul_add_t(const uint64_t acc[8], const uint64_t scalar[4], const uint64_t point[8], uint64_t out[8]) {
+    HOSTF_REGION("g1");
     hostf::to_affine(hostf::add_pt(g1_straus<FB, FS>(scalar, point, 1), lift_affine<FB>(acc)), out);
 }
 // acc + sum_i scalars[i] * points[i] on affine points: the instance side of a fold, E_commit + sum_k r^(k+1) T_k over the
@@ -203,6 +207,7 @@ template <class FB, class FS> static void g1_mul_add_t(const uint64_t acc[8], co
 // thread walks ONE chain of doublings for its terms.
 template <class FB, class FS> static hostf::HXyzz<FB> g1_lincomb_xyzz(const uint64_t *scalars, const uint64_t *points, size_t count) {
     using namespace hostf;
+    HOSTF_REGION("g1");
     const size_t groups = std::min<size_t>(count, host_parallel_width());
     if (groups <= 1) return g1_straus<FB, FS>(scalars, points, count);
     std::vector<HXyzz<FB>> part(groups);
@@ -216,6 +221,7 @@ template <class FB, class FS> static hostf::HXyzz<FB> g1_lincomb_xyzz(const uint
 }
 template <class FB, class FS>
 static void g1_lincomb_t(const uint64_t acc[8], const uint64_t *scalars, const uint64_t *points, size_t count, uint64_t out[8]) {
+    HOSTF_REGION("g1");
     hostf::to_affine(hostf::add_pt(g1_lincomb_xyzz<FB, FS>(scalars, points, count), lift_affine<FB>(acc)), out);
 }
 // RelaxedPlonkInstance::fold, the commitments (src/plonk/mod.rs:986-999: W1_i + r W2_i; :1049-1053: E + sum_k r^(k+1) T_k),
@@ -224,6 +230,7 @@ template <class FB, class FS>
 static void g1_fold_commitments_t(const uint64_t r[4], const uint64_t *w1, const uint64_t *w2, size_t nw, const uint64_t e[8], const uint64_t *t_commits,
                                   size_t count, uint64_t *w_out, uint64_t e_out[8]) {
     using namespace hostf;
+    HOSTF_REGION("g1");
     std::vector<uint64_t> powers(4 * count);
     HFe<FS> rr, p;
     memcpy(rr.l, r, 32);

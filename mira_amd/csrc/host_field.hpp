@@ -8,6 +8,9 @@
 #include <cstring>
 
 #include "field.cuh"
+#if defined(MIRA_CPU_EMU) && defined(F29_TRACK)
+#include "f29_census.h"   // test-only branch census: HOSTF_HIT below
+#endif
 
 namespace hostf {
 typedef unsigned __int128 u128;
@@ -120,15 +123,24 @@ template <class FP> inline HFe<FP> inv(const HFe<FP> &a) {
     return pow(a, e);
 }
 
+// branch census of the host group law, as F29_HIT in field29.cuh: nothing outside the test-only emulation build
+#if defined(MIRA_CPU_EMU) && defined(F29_TRACK)
+#define HOSTF_HIT(fn, site) emu_hit(fn, site)
+#define HOSTF_REGION(name) EMU_REGION_SCOPE(name)
+#else
+#define HOSTF_HIT(fn, site) ((void)0)
+#define HOSTF_REGION(name) ((void)0)
+#endif
 template <class FP> struct HXyzz {
     HFe<FP> x, y, zz, zzz;
 };
 template <class FP> inline HXyzz<FP> identity() { HXyzz<FP> r; memset(&r, 0, sizeof r); return r; }
 template <class FP> inline bool is_identity(const HXyzz<FP> &p) { return is_zero(p.zz); }
 template <class FP> inline HXyzz<FP> dbl_pt(const HXyzz<FP> &p) {   // dbl-2008-s-1
-    if (is_identity(p)) return p;
+    if (is_identity(p)) { HOSTF_HIT("dbl_pt", "identity_in"); return p; }
     HFe<FP> u = dbl(p.y);
-    if (is_zero(u)) return identity<FP>();
+    if (is_zero(u)) { HOSTF_HIT("dbl_pt", "identity_out"); return identity<FP>(); }
+    HOSTF_HIT("dbl_pt", "common");
     HFe<FP> v = sqr(u), w = mul(u, v), s = mul(p.x, v), xx = sqr(p.x), m = add(dbl(xx), xx);
     HXyzz<FP> r;
     r.x = sub(sqr(m), dbl(s));
@@ -137,11 +149,16 @@ template <class FP> inline HXyzz<FP> dbl_pt(const HXyzz<FP> &p) {   // dbl-2008-
     return r;
 }
 template <class FP> inline HXyzz<FP> add_pt(const HXyzz<FP> &a, const HXyzz<FP> &b) {   // add-2008-s
-    if (is_identity(b)) return a;
-    if (is_identity(a)) return b;
+    if (is_identity(b)) { HOSTF_HIT("add_pt", "identity_in"); return a; }
+    if (is_identity(a)) { HOSTF_HIT("add_pt", "identity_in"); return b; }
     HFe<FP> u1 = mul(a.x, b.zz), u2 = mul(b.x, a.zz), s1 = mul(a.y, b.zzz), s2 = mul(b.y, a.zzz);
     HFe<FP> p = sub(u2, u1), r = sub(s2, s1);
-    if (is_zero(p)) return is_zero(r) ? dbl_pt(a) : identity<FP>();
+    if (is_zero(p)) {
+        if (is_zero(r)) { HOSTF_HIT("add_pt", "same"); return dbl_pt(a); }
+        HOSTF_HIT("add_pt", "opposite");
+        return identity<FP>();
+    }
+    HOSTF_HIT("add_pt", "common");
     HFe<FP> pp = sqr(p), ppp = mul(p, pp), q = mul(u1, pp);
     HXyzz<FP> o;
     o.x = sub(sub(sqr(r), ppp), dbl(q));

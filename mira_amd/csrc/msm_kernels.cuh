@@ -597,6 +597,7 @@ DEV void fixup_light(uint32_t gid, uint32_t nquads, const uint32_t *__restrict__
                      const unsigned char *__restrict__ head_part, const unsigned char *__restrict__ tail_part,
                      const uint32_t *__restrict__ tail_key, unsigned char *__restrict__ bucket_sums, uint32_t num_buckets,
                      const uint32_t *__restrict__ heavy_ctr, const U4 *__restrict__ meds) {
+    F29_REGION("light");
     // the medium runs, when there are many: dealt to the quads of the light section
     const uint32_t n_medium = heavy_ctr[5];
     if (medium_as_chains(heavy_ctr))
@@ -680,6 +681,7 @@ template <class F>
 DEV void fixup_heavy_a(uint32_t block, uint32_t nblocks, unsigned char *red, const uint32_t *__restrict__ heavy_ctr, const U4 *__restrict__ subs, const U4 *__restrict__ runs,
                        const unsigned char *__restrict__ head_part, const unsigned char *__restrict__ tail_part,
                        unsigned char *__restrict__ sub_out, unsigned char *__restrict__ bucket_sums, const U4 *__restrict__ meds) {
+    F29_REGION("heavy_a");
     // sub-jobs [0, nheavy) come from the heavy runs; a FEW medium runs follow them as sub-jobs of their own (one each)
     const uint32_t nheavy = heavy_ctr[1], n_medium = heavy_ctr[5], qi = threadIdx.x >> 2;
     const uint32_t nsubs = nheavy + (medium_as_chains(heavy_ctr) ? 0u : n_medium);

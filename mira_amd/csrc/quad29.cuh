@@ -54,7 +54,8 @@ DEV void quad_mul4(const Fe29<F> &a0, const Fe29<F> &b0, const Fe29<F> &a1, cons
 
 // 2 * XYZZ: dbl-2008-s-1 in three levels (curve29.cuh's xyzz29_double lists the bounds)
 template <class F> DEV Xyzz29<F> xyzz29_double_quad(const Xyzz29<F> &p) {
-    if (xyzz29_is_identity(p)) return p;
+    if (xyzz29_is_identity(p)) { F29_HIT("double_quad", "identity_in"); return p; }
+    F29_HIT("double_quad", "common");
     Xyzz29<F> r;
     const Fe29<F> u = f29_dbl(p.y);                               // < 10
     Fe29<F> v, xx, t0, t1;
@@ -71,17 +72,18 @@ template <class F> DEV Xyzz29<F> xyzz29_double_quad(const Xyzz29<F> &p) {
 
 // acc += q (both XYZZ): add-2008-s in four levels
 template <class F> DEV void xyzz29_add_quad(Xyzz29<F> &acc, const Xyzz29<F> &q) {
-    if (xyzz29_is_identity(q)) return;
-    if (xyzz29_is_identity(acc)) { acc = q; return; }
+    if (xyzz29_is_identity(q)) { F29_HIT("add_quad", "identity_in"); return; }
+    if (xyzz29_is_identity(acc)) { F29_HIT("add_quad", "identity_in"); acc = q; return; }
     Fe29<F> u1, u2, s1, s2;
     quad_mul4(acc.x, q.zz, q.x, acc.zz, acc.y, q.zzz, q.y, acc.zzz, u1, u2, s1, s2);   // 18, 18, 10, 10
     const Fe29<F> p = f29_sub<3>(u2, u1);                         // < 5
     const Fe29<F> r = f29_sub<3>(s2, s1);                         // < 5
     if (f29_is_zero_mod_p<5>(p)) {
-        if (f29_is_zero_mod_p<5>(r)) acc = xyzz29_double_quad(acc);
-        else acc = xyzz29_identity<F>();
+        if (f29_is_zero_mod_p<5>(r)) { F29_HIT("add_quad", "same"); acc = xyzz29_double_quad(acc); }
+        else { F29_HIT("add_quad", "opposite"); acc = xyzz29_identity<F>(); }
         return;
     }
+    F29_HIT("add_quad", "common");
     Fe29<F> pp, rr, zz12, zzz12;
     quad_mul4(p, p, r, r, acc.zz, q.zz, acc.zzz, q.zzz, pp, rr, zz12, zzz12);          // 25, 25, 4, 4
     Fe29<F> ppp, qq, t0;

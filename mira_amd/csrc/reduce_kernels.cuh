@@ -34,6 +34,7 @@ struct PieceCfg {
 // into ONE node of S0 + levels components at slot 0.  A node of level k owns the S0 2^k slots of its leaves and
 // holds S0 + k components at their start.  Block-uniform control flow (barriers inside).
 template <class F> DEV void node_tree_quad(unsigned char *slots, uint32_t S0, uint32_t levels) {
+    F29_REGION("node_tree");
     const uint32_t qi = threadIdx.x >> 2, nq = blockDim.x >> 2;
     for (uint32_t k = 0; k < levels; k++) {
         const uint32_t parents = 1u << (levels - 1 - k), comps = S0 + k, span = S0 << k;
@@ -66,6 +67,7 @@ KERNEL void __launch_bounds__(512) k_bucket_tree(const unsigned char *__restrict
     DYN_SHARED(unsigned char, slots);
     const uint32_t m = 1u << lambda;
     const uint32_t item = QUAD ? threadIdx.x >> 2 : threadIdx.x;
+    F29_REGION("phase_a");
     if (item < (1u << kappa)) {                              // (a workgroup has at least one quad: more lanes than chunks when kappa < 2)
         const size_t chunk = ((size_t)blockIdx.x << kappa) + item;
         const unsigned char *S = bucket_sums + (chunk << lambda) * XYZZ29_BYTES;
@@ -118,6 +120,7 @@ KERNEL void __launch_bounds__(512) k_set_finish(const unsigned char *__restrict_
     __syncthreads();
     node_tree_quad<F>(slots, S0, gamma);
     const uint32_t p = threadIdx.x >> 2;
+    F29_REGION("horner");
     if (p < pc.P) {
         // Horner over the bit positions of the piece, highest first; positions 1 .. lambda - 1 hold nothing
         Xyzz29<F> acc = xyzz29_identity<F>();

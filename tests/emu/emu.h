@@ -56,7 +56,11 @@ typedef void *hipStream_t;
 typedef int hipError_t;
 #define hipSuccess 0
 
-template <class F> void emu_launch(bool barrier, dim3 grid, dim3 block, size_t shmem, F &&body) {
+// the branch census (mira_amd/csrc/f29_census.h) counts under the kernel a launch names
+#include "../../mira_amd/csrc/f29_census.h"
+
+template <class F> void emu_launch(const char *name, bool barrier, dim3 grid, dim3 block, size_t shmem, F &&body) {
+    EmuKernelScope scope(name);                              // the lanes of a plain launch run on this thread
     gridDim = grid; blockDim = block;
     std::vector<unsigned char> sh(shmem + 16);
     emu_dyn_shared = sh.data();
@@ -81,6 +85,7 @@ template <class F> void emu_launch(bool barrier, dim3 grid, dim3 block, size_t s
     th.reserve(nthreads);
     for (unsigned t = 0; t < nthreads; t++)
         th.emplace_back([&, t] {
+            EmuKernelScope lane_scope(name);
             threadIdx = tid3(t);
             for (unsigned bz = 0; bz < grid.z; bz++)
                 for (unsigned by = 0; by < grid.y; by++)
@@ -95,9 +100,9 @@ template <class F> void emu_launch(bool barrier, dim3 grid, dim3 block, size_t s
     emu_barrier = nullptr;
 }
 #define LAUNCH(kern, grid, block, shmem, stream, ...) \
-    emu_launch(false, dim3(grid), dim3(block), (shmem), [&] { kern(__VA_ARGS__); })
+    emu_launch(#kern, false, dim3(grid), dim3(block), (shmem), [&] { kern(__VA_ARGS__); })
 #define LAUNCH_BARRIER(kern, grid, block, shmem, stream, ...) \
-    emu_launch(true, dim3(grid), dim3(block), (shmem), [&] { kern(__VA_ARGS__); })
+    emu_launch(#kern, true, dim3(grid), dim3(block), (shmem), [&] { kern(__VA_ARGS__); })
 // blockDim-agnostic kernels run with a handful of lanes under emulation (OS threads are costly)
 #define LAUNCH_BARRIER_FLEX(kern, grid, block, shmem, stream, ...) \
-    emu_launch(true, dim3(grid), dim3(std::min<unsigned>((block), 8u)), (shmem), [&] { kern(__VA_ARGS__); })
+    emu_launch(#kern, true, dim3(grid), dim3(std::min<unsigned>((block), 8u)), (shmem), [&] { kern(__VA_ARGS__); })

@@ -37,6 +37,12 @@ def ints_to_mont(vals, mod):
     return np.array([P.limbs4(P.to_mont(v, mod)) for v in vals], dtype=np.uint64).reshape(-1, 4)
 
 
+def glv_edge_scalars(r):
+    """canonical scalars around the edges of the GLV decomposition: the 126-, 127- and 128-bit boundaries of the two halves, the
+    ends of the field, bit 253"""
+    return [0, 1, 2, (1 << 126) - 1, 1 << 126, (1 << 127) - 1, 1 << 127, (1 << 128) + 5, r - 1, r - 2, 1 << 253, (1 << 253) + 12345]
+
+
 def mont_to_ints(arr, mod):
     return [P.from_mont(P.from_limbs4(row), mod) for row in np.asarray(arr, dtype=np.uint64).reshape(-1, 4)]
 

@@ -156,6 +156,61 @@ def test_emu_fold_instance_commitments_matches_oracle(emu_lib):
             _instance_fold_case(cid, emu_lib, nw, count, seed=30 + nw * 7 + count)
 
 
+def _host_group_cases(cid, lib):
+    """mira_g1_mul_add, mira_g1_lincomb and mira_g1_fold_commitments on multiples of G, against Python integers: every expected
+    point is (the integer combination mod r) G by oracle/pyref.py"""
+    cv = P.CURVES[cid]
+    r = cv.r
+    pt = lambda m: point_to_arr(P.ec_mul(m % r, cv.gen, cv), cid)          # 0 -> the identity, all zero
+    sc = lambda vals: ints_to_mont([v % r for v in vals], r)
+    # acc + s P: identity on either side, equal points (1 + 1 * 1), opposite points (1 + (r - 1) * 1, 5 + 1 * -5), a term equal to
+    # the accumulator (10 + 2 * 5), scalars 0, 1 and r - 1
+    for a in (0, 1, -1, 5, 10):
+        for b in (0, 1, -1, 5, -5):
+            for s in (0, 1, 2, r - 1):
+                got = FD.g1_mul_add(cid, pt(a), sc([s])[0], pt(b), lib=lib)
+                assert (got == pt(a + s * b)).all(), (cid, a, b, s)
+    # Straus over shared doublings: terms that cancel pairwise (every digit position adds d P and then -d P), equal terms (the
+    # accumulator meets the table entry it already holds), identity terms, a sum equal or opposite to the accumulator, no terms
+    lincombs = [(0, [7, 7, 12345, r - 12345], [1, -1, 3, 3]), (0, [1, 1], [1, 1]), (0, [1, 1, 1], [1, 1, -2]), (4, [2, 0, r - 1], [-2, 5, 0]),
+                (9, [3, r - 1, 1], [3, 0, 2]), (-6, [3, 3], [1, 1]), (6, [3, 3], [1, 1]), (0, [0, 0], [1, 2]), (5, [], []), (0, [], []),
+                (1, [r - 1, r - 1, 2], [1, -1, 0]), (0, [(1 << 253) + 15, (1 << 253) + 15, 31, 31], [2, -2, 1, -1]), (2, [15, 17, 16], [1, 1, -2])]
+    for a, ks, ms in lincombs:
+        terms = np.stack([pt(m) for m in ms]) if ms else np.zeros((0, 8), dtype=np.uint64)
+        scalars = sc(ks) if ks else np.zeros((0, 4), dtype=np.uint64)
+        got = FD.g1_lincomb(cid, pt(a), scalars, terms, lib=lib)
+        assert (got == pt(a + sum(k * m for k, m in zip(ks, ms)))).all(), (cid, a, ks, ms)
+    # W1_i + rho W2_i and E + sum_k rho^(k+1) T_k: rho = 1 (equal points double), rho = r - 1 (opposite points and cross terms that
+    # cancel pairwise), rho = 0, identity commitments
+    for rho in (1, r - 1, 0, 2):
+        w1, w2 = [1, 1, 0, 5, -3, 2], [1, -1, 7, 0, 3, 1]
+        for e, ts in ((0, [1, 1, 4, 4]), (3, [3]), (-3, [3, 0]), (0, []), (2, [1, -1, 1, -1, 2]), (0, [0, 0, 0])):
+            t = np.stack([pt(m) for m in ts]) if ts else np.zeros((0, 8), dtype=np.uint64)
+            w_out, e_out = FD.fold_instance_commitments(cid, np.stack([pt(m) for m in w1]), np.stack([pt(m) for m in w2]), sc([rho])[0], pt(e), t, lib=lib)
+            for i, (a, b) in enumerate(zip(w1, w2)):
+                assert (w_out[i] == pt(a + rho * b)).all(), (cid, rho, a, b)
+            assert (e_out == pt(e + sum(pow(rho, k + 1, r) * m for k, m in enumerate(ts)))).all(), (cid, rho, e, ts)
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_emu_host_group_ops_on_exceptional_points(emu_lib, cid):
+    """The exceptional branches of the host group law (host_field.hpp: add_pt, dbl_pt) behind the instance side of a fold; the
+    emulation's branch census shows that the cases reached every one of them (dbl_pt's exit for a point of order two cannot be
+    reached: both groups have odd prime order)."""
+    import exceptional_points as X
+    X.census_reset(emu_lib)
+    _host_group_cases(cid, emu_lib)
+    seen = {(fn, site) for (kernel, section, fn, site), hits in X.census_read(emu_lib).items() if kernel == "host" and section == "g1" and hits}
+    assert seen == {("add_pt", "identity_in"), ("add_pt", "same"), ("add_pt", "opposite"), ("add_pt", "common"), ("dbl_pt", "identity_in"), ("dbl_pt", "common")}
+
+
+def test_product_host_group_ops_on_exceptional_points():
+    """the same cases through libmira_gpu.so (host arithmetic: no device call), on the library's resident threads"""
+    from mira_amd import _lib
+    for cid in (0, 1):
+        _host_group_cases(cid, _lib.load())
+
+
 def test_product_host_fold_runs_on_its_threads():
     """The same calls through libmira_gpu.so: these entry points are host arithmetic (no device call), and in the product
     build their terms are dealt to the library's resident threads -- the points must not depend on how."""

@@ -5,7 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from helpers import arr_to_point, golden_msm_case, ints_to_mont, load_golden, mont_to_ints, point_to_arr
+from helpers import arr_to_point, glv_edge_scalars, golden_msm_case, ints_to_mont, load_golden, mont_to_ints, point_to_arr
 from mira_amd import commitment as cm
 from mira_amd import _lib
 from oracle import cref as C
@@ -382,7 +382,7 @@ def test_glv_split_every_width(gpu_lib, cid, log_n):
     d = cm.synth_scalars_device(cid, n, seed=142)
     dw = cm.synth_scalars_device(cid, n, seed=143, kind=1)
     sc = gpu_lib.download(d, (n, 4))
-    edge = [0, 1, 2, (1 << 126) - 1, 1 << 126, (1 << 127) - 1, 1 << 127, (1 << 128) + 5, r - 1, r - 2, 1 << 253, (1 << 253) + 12345]
+    edge = glv_edge_scalars(r)
     se = sc.copy()
     se[1000:1000 + 64 * len(edge)] = np.tile(ints_to_mont(edge, r), (64, 1))
     de = gpu_lib.alloc(n * 32); gpu_lib.upload(de, se)
