@@ -225,6 +225,11 @@ int mira_msm_last_table_bits(int32_t *table_bits);
 /* elements per lane of every level of a batch inversion (mira_batch_invert_device, mira_lookup_h_g_device), 2 .. 64, default 8.
  * Never changes a result */
 #define MIRA_TUNE_INV_CHUNK 22
+/* workgroups of one sweep of the deciders (mira_count_ne_device, mira_sum_sub_device, mira_graph_check_compiled,
+ * mira_perm_check_device), 1 .. 2048 (0 or more -> MIRA_E_BAD_ARG; negative restores the default: one per 256 elements, at
+ * most 2048).  Tests use it to reach several workgroups at small sizes.
+ * Never changes a result */
+#define MIRA_TUNE_DECIDE_GRID 23
 int mira_set_tuning(int knob, int64_t value);
 
 /* Read a range of the registered key back in the reference layout (cache file writing,
@@ -387,6 +392,44 @@ int mira_graph_jit_source(uint64_t handle, const mira_eval_column *columns, uint
 int mira_graph_set_cache_dir(const char *dir);
 int mira_graph_jit_stats(uint32_t *compiled_out, uint32_t *from_disk_out);
 int mira_graph_jit_compile_check(const char *source, size_t *code_size_out);
+
+/* ---- the deciders on device-resident vectors (src/plonk/mod.rs:434-622) ------------------------
+ * What IVC::verify (src/ivc/incrementally_verifiable_computation.rs:617-680) runs over the witness vectors a fold step left
+ * in HBM, without copying them to the host.  Vectors of 32-byte Montgomery elements, field MIRA_FIELD_FQ / MIRA_FIELD_FR;
+ * equality is decided on the representation, as PartialEq on the canonical limbs does.  n = 0 is a no-op with count 0 and sum 0;
+ * a null pointer with n > 0 or an unknown field -> MIRA_E_BAD_ARG; an input element >= the modulus -> MIRA_E_BAD_ARG, the
+ * outputs are then unspecified.  Counts, first indices and sums are exact and do not depend on scheduling (no global atomics:
+ * one partial record per workgroup, folded by one more workgroup; field addition is associative).
+ *
+ * mira_count_ne_device: the count of i < n with a[i] != b[i] (d_b NULL: a[i] != 0) and the smallest such i (UINT64_MAX if
+ * none; the reference warn!s the row, mod.rs:526) -- the compare half of the row sweeps and of any vector comparison.
+ * mira_sum_sub_device: out = sum a[i] - sum b[i] (d_b NULL: sum a[i]), canonical Montgomery: the per-lookup sum of
+ * is_sat_log_derivative (mod.rs:592-622), zero iff the lookup is satisfied.
+ * mira_graph_check_compiled: the row sweep of is_sat (d_expected NULL, mod.rs:458-478) / is_sat_relaxed (d_expected = W.E,
+ * mod.rs:516-541): evaluates a compiled graph over all rows into library scratch -- through a specialised kernel when the
+ * handle has one, exactly as mira_graph_eval_compiled does -- and counts the rows that differ from 0 / from d_expected:
+ * Error::EvaluationMismatch { mismatch_count, total_row = num_rows }. */
+int mira_count_ne_device(int field, const void *d_a, const void *d_b /* may be NULL */, size_t n, uint64_t *count_out, uint64_t *first_out /* may be NULL */);
+int mira_sum_sub_device(int field, const void *d_a, const void *d_b /* may be NULL */, size_t n, uint64_t out[4]);
+int mira_graph_check_compiled(uint64_t handle, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges,
+                              uint32_t num_challenges, size_t num_rows, const void *d_expected /* may be NULL */, uint64_t *mismatch_out,
+                              uint64_t *first_row_out /* may be NULL */);
+/* is_sat_perm (mod.rs:563-589): y = P Z by matrix_multiply (src/polynomial/sparse.rs:7-19), count of y_i != Z_i ->
+ * Error::PermCheckFail { mismatch_count }.
+ * mira_perm_compile, once per circuit (PlonkStructure::permutation_matrix is fixed): the triples (row, col, value) of an
+ * n x n SparseMatrix, host memory; values: nnz * 4 limbs, Montgomery, or NULL = all ONE.  row >= n or col >= n ->
+ * MIRA_E_BAD_ARG (the reference panics "invalid matrix multiply"); n or nnz >= 2^32 -> MIRA_E_UNSUPPORTED.  Triples in any
+ * order; duplicates of (row, col) add, as the reference's loop does; a row without a triple gives y_i = 0.  A matrix whose
+ * every row holds exactly one entry of value ONE (construct_permutation_matrix + fill_sparse_matrix, src/plonk/util.rs:44-71,
+ * 128-174) is kept as one u32 per row, any other as CSR with the values in multiplier form.
+ * mira_perm_check_device: Z = instance (host, num_io elements) || d_w (device, n_w elements: W[0][..2^k * num_advice]); Z is
+ * never materialised.  num_io + n_w != n -> MIRA_E_BAD_ARG.
+ * mira_perm_free: releases the compiled matrix. */
+int mira_perm_compile(int field, const uint64_t *rows, const uint64_t *cols, const uint64_t *values /* nnz * 4 or NULL */, size_t nnz, size_t n,
+                      uint64_t *handle_out);
+int mira_perm_check_device(uint64_t handle, const uint64_t *instance, size_t num_io, const void *d_w, size_t n_w, uint64_t *mismatch_out,
+                           uint64_t *first_out /* may be NULL */);
+int mira_perm_free(uint64_t handle);
 
 
 /* ---- ProtoGalaxy's polynomial pipeline around the NTT (src/nifs/protogalaxy/poly/mod.rs) -------

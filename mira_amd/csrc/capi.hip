@@ -586,7 +586,8 @@ int mira_msm_combine(int curve, const uint64_t *partials, size_t nparts, int32_t
 }
 int mira_set_tuning(int knob, int64_t value) {
     std::lock_guard<std::mutex> lk(g_lock);
-    if (knob < 0 || knob > MIRA_TUNE_INV_CHUNK || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
+    if (knob < 0 || knob > MIRA_TUNE_DECIDE_GRID || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
+    if (knob == MIRA_TUNE_DECIDE_GRID && (value == 0 || value > 2048)) { set_error("MIRA_TUNE_DECIDE_GRID takes 1 .. 2048 workgroups (negative: the default)"); return MIRA_E_BAD_ARG; }
     g.tune[knob] = value;
     return MIRA_OK;
 }
@@ -708,7 +709,7 @@ int mira_trim(size_t keep_bytes, size_t *released_out) {
     std::vector<DevBuf *> bufs = {&g.digits, &g.counts, &g.offsets, &g.cursor, &g.block_sums, &g.sorted_idx, &g.bucket_sums, &g.part, &g.coarse_offsets,
                                   &g.fine_counts, &g.fine_cursor, &g.head_part, &g.tail_part, &g.tail_key, &g.heavy, &g.heavy_out, &g.chunks, &g.window_sums,
                                   &g.scalars_stage, &g.ntt_tmp, &g.ntt_stage, &g.graph_ws, &g.tree_a, &g.tree_b, &g.hist_dev,
-                                  &g.inv_ws, &g.lk_owner, &g.lk_first, &g.lk_count, &g.lk_slot};
+                                  &g.inv_ws, &g.lk_owner, &g.lk_first, &g.lk_count, &g.lk_slot, &g.decide_parts, &g.decide_eval, &g.decide_inst};
     for (int i = 0; i < Ctx::NTT_SETS; i++) bufs.push_back(&g.ntt_set[i]);
     size_t total = 0;
     for (DevBuf *b : bufs) total += b->cap;
@@ -844,6 +845,58 @@ int mira_lookup_h_g_device(int field, void *d_h, void *d_g, const void *d_l, siz
         if (rw[k] != P[k]) { below = rw[k] < P[k]; break; }
     if (!below) { set_error("r is not canonical (>= the modulus)"); return MIRA_E_BAD_ARG; }
     return lookup_h_g_device(field, d_h, d_g, d_l, n_l, d_t, d_m, n_t, r);
+}
+// ---- deciders (decide.hip)
+int mira_count_ne_device(int field, const void *d_a, const void *d_b, size_t n, uint64_t *count_out, uint64_t *first_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!lk_field_ok(field) || !count_out || (n && !d_a)) { set_error("bad count_ne arguments"); return MIRA_E_BAD_ARG; }
+    if (!n) { *count_out = 0; if (first_out) *first_out = UINT64_MAX; return MIRA_OK; }
+    return count_ne_device(field, d_a, d_b, n, count_out, first_out);
+}
+int mira_sum_sub_device(int field, const void *d_a, const void *d_b, size_t n, uint64_t out[4]) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!lk_field_ok(field) || !out || (n && !d_a)) { set_error("bad sum_sub arguments"); return MIRA_E_BAD_ARG; }
+    if (!n) { memset(out, 0, 32); return MIRA_OK; }
+    return sum_sub_device(field, d_a, d_b, n, out);
+}
+int mira_graph_check_compiled(uint64_t handle, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges, uint32_t num_challenges,
+                              size_t num_rows, const void *d_expected, uint64_t *mismatch_out, uint64_t *first_row_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if ((num_columns && !columns) || (num_challenges && !challenges) || !mismatch_out) { set_error("bad graph check arguments"); return MIRA_E_BAD_ARG; }
+    int field = 0;
+    if ((rc = graph_field(handle, &field))) return rc;
+    if ((rc = g.decide_eval.ensure(std::max<size_t>(num_rows, 1) * 32))) return rc;
+    // the evaluation itself is mira_graph_eval_compiled's, specialised kernel included; the compare re-reads it (64 B per row)
+    if ((rc = graph_eval_compiled(handle, columns, num_columns, challenges, num_challenges, num_rows, g.decide_eval.p))) return rc;
+    if (!num_rows) { *mismatch_out = 0; if (first_row_out) *first_row_out = UINT64_MAX; return MIRA_OK; }
+    return count_ne_device(field, g.decide_eval.p, d_expected, num_rows, mismatch_out, first_row_out);
+}
+int mira_perm_compile(int field, const uint64_t *rows, const uint64_t *cols, const uint64_t *values, size_t nnz, size_t n, uint64_t *handle_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!lk_field_ok(field) || !handle_out || (nnz && (!rows || !cols))) { set_error("bad permutation matrix arguments"); return MIRA_E_BAD_ARG; }
+    if ((uint64_t)n >= (1ull << 32) || (uint64_t)nnz >= (1ull << 32)) { set_error("permutation matrices of 2^32 rows or entries or more are not supported"); return MIRA_E_UNSUPPORTED; }
+    return perm_compile(field, rows, cols, values, nnz, n, handle_out);
+}
+int mira_perm_check_device(uint64_t handle, const uint64_t *instance, size_t num_io, const void *d_w, size_t n_w, uint64_t *mismatch_out, uint64_t *first_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!mismatch_out || (num_io && !instance) || (n_w && !d_w)) { set_error("bad permutation check arguments"); return MIRA_E_BAD_ARG; }
+    return perm_check_device(handle, instance, num_io, d_w, n_w, mismatch_out, first_out);
+}
+int mira_perm_free(uint64_t handle) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    return perm_free(handle);
 }
 int mira_lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint64_t *coeffs, size_t num_vecs, size_t n) {
     std::lock_guard<std::mutex> lk(g_lock);

@@ -131,6 +131,7 @@ struct Ctx {
     DevBuf tree_w, tree_a, tree_b;   // weighted tree reduction: level weights, ping-pong partial results
     DevBuf inv_ws;                   // batch inversion: upper levels' values and prefix products (lookup.hip)
     DevBuf lk_owner, lk_first, lk_count, lk_slot, lk_err;   // the multiplicities' hash table, every t element's slot, the error word
+    DevBuf decide_parts, decide_eval, decide_inst;   // deciders (decide.hip): result + partial records, the row sweep's evaluation, the uploaded instance
     uint32_t hist_host[256] = {};    // the statistics of the last commit that collected them
     int32_t last_c = 0, last_w = 0;  // mira_msm_last_plan
     int32_t last_table_c = 0;        // mira_msm_last_table_bits: width of the table set the last commit went through, 0 = none
@@ -295,6 +296,7 @@ int fold_witness_device(int field, void *d_out, const void *d_w1, const void *d_
 int fold_error_device(int field, void *d_e, const void *const *d_terms, size_t K, const uint64_t r[4], size_t n);
 int fold_relaxed_device(int field, void *d_w_out, const void *d_w1, const void *d_w2, size_t n_w, void *d_e_out, const void *d_e, const void *const *d_terms, size_t K,
                         const uint64_t r[4], size_t n);
+void to_mult48(int field, const uint64_t v_r256[4], uint32_t out[12]);   // reference form -> the 48-byte multiplier form fold_const_load reads
 int lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint64_t *coeffs, size_t K, size_t n);
 int lincomb_multi_device(int field, void *const *d_outs, size_t M, const void *const *d_vecs, size_t J, const uint64_t *coeffs, size_t n);
 int pow_tree_reduce_device(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out);
@@ -304,11 +306,19 @@ int batch_invert_device(int field, void *d_out, const void *d_in, size_t n);
 int lookup_m_device(int field, void *d_m, const void *d_l, size_t n_l, const void *d_t, size_t n_t);
 int lookup_h_g_device(int field, void *d_h, void *d_g, const void *d_l, size_t n_l, const void *d_t, const void *d_m, size_t n_t, const uint64_t r[4]);
 
+// decide.hip
+int count_ne_device(int field, const void *d_a, const void *d_b, size_t n, uint64_t *count_out, uint64_t *first_out);
+int sum_sub_device(int field, const void *d_a, const void *d_b, size_t n, uint64_t out[4]);
+int perm_compile(int field, const uint64_t *rows, const uint64_t *cols, const uint64_t *values, size_t nnz, size_t n, uint64_t *handle_out);
+int perm_check_device(uint64_t handle, const uint64_t *instance, size_t num_io, const void *d_w, size_t n_w, uint64_t *mismatch_out, uint64_t *first_out);
+int perm_free(uint64_t handle);
+
 // graph.hip
 int graph_compile(int field, const mira_graph *gr, uint32_t num_challenges, uint32_t num_columns, uint64_t *handle_out);
 int graph_eval_compiled(uint64_t handle, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges, uint32_t num_challenges,
                         size_t num_rows, void *d_out);
 int graph_free(uint64_t handle);
+int graph_field(uint64_t handle, int *field_out);
 int graph_eval_batch(const uint64_t *handles, uint32_t count, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges,
                      uint32_t num_challenges, size_t num_rows, void *const *d_outs);
 int graph_specialize(const uint64_t *handles, uint32_t count, const mira_eval_column *columns, uint32_t num_columns,

@@ -16,6 +16,9 @@ template <class FP> static void to_mult48(const uint64_t v_r256[4], uint32_t out
         out[i] = (uint32_t)(v & 0x1FFFFFFFu);
     }
 }
+void to_mult48(int field, const uint64_t v_r256[4], uint32_t out[12]) {
+    if (field == MIRA_FIELD_FR) to_mult48<FrP>(v_r256, out); else to_mult48<FqP>(v_r256, out);
+}
 static uint32_t fold_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(256 * 8, (n + 255) / 256); }
 
 template <class F, class FP> static int fold_witness_t(void *d_out, const void *d_w1, const void *d_w2, const uint64_t r[4], size_t n) {

@@ -121,6 +121,13 @@ int graph_free(uint64_t handle) {
     return MIRA_OK;
 }
 
+int graph_field(uint64_t handle, int *field_out) {
+    auto it = g_programs.find(handle);
+    if (it == g_programs.end()) { set_error("unknown graph handle"); return MIRA_E_BAD_ARG; }
+    *field_out = it->second.field;
+    return MIRA_OK;
+}
+
 // count compiled graphs over the same columns and challenges, results to d_outs[k]; one launch per
 // GRAPH_MAX_BATCH graphs
 int graph_eval_batch(const uint64_t *handles, uint32_t count, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges,

@@ -124,6 +124,20 @@ class GraphEvaluator:
             raise
         return out
 
+    def check_device(self, columns, challenges, num_rows, d_expected=None, lib=None):
+        """mira_graph_check_compiled: the row sweep of is_sat (d_expected None: rows where the graph is not 0,
+        src/plonk/mod.rs:458-478) or is_sat_relaxed (d_expected = E on the device: rows where it differs from E[row],
+        :516-541).  The evaluation goes to library scratch, nothing comes back but (mismatch_count, first_row);
+        first_row is 2^64 - 1 when no row differs.  columns, challenges: as for `evaluate_device`."""
+        lib = lib or _lib.load()
+        handle = self.compiled(len(challenges), len(columns), lib)
+        cols = GraphEvaluator._column_table(columns)
+        ch = to_montgomery(list(challenges), self.field)
+        count, first = ctypes.c_uint64(), ctypes.c_uint64()
+        lib.check(lib.c.mira_graph_check_compiled(handle, cols, len(columns), ch.ctypes.data_as(ctypes.c_void_p), len(ch), num_rows,
+                                                  ctypes.c_void_p(d_expected), ctypes.byref(count), ctypes.byref(first)))
+        return count.value, first.value
+
     @staticmethod
     def evaluate_batch_device(evaluators, columns, challenges, num_rows, d_outs, lib=None):
         """The cross-term graphs of one fold step (src/nifs/vanilla/mod.rs:100-121 walks them one after
