@@ -5,7 +5,7 @@
 #include "ctx.h"
 #include "glv_consts.h"
 #include "host_curve.hpp"
-#include "msm_plan.h"
+#include "msm_route.h"
 #include <cerrno>
 #include <chrono>
 #include <fcntl.h>
@@ -49,9 +49,6 @@ void set_error(const std::string &s) { g_err = s; }
 static std::mutex g_lock;
 Ctx g;
 static std::map<uint64_t, Bases> g_bases;
-static constexpr size_t PLAN_HIST_MIN_N = (size_t)1 << 15;  // below this the pre-pass (one extra sync) costs more than it can save
-static constexpr size_t TABLE_MIN_N = (size_t)1 << 18;   // below this an MSM is latency-bound and the per-window path is as fast
-static constexpr size_t TABLE16_MIN_N = (size_t)1 << 12;
 
 static int upload_consts();   // the device constants block (ctx.h: DevConsts)
 
@@ -146,7 +143,22 @@ static int upload_consts() {
 }
 
 // ------------------------------------------------------------------------------------------
-// MSM route (the planner: msm_plan.hip)
+// argument checks every entry point shares
+static bool curve_ok(int curve) { return curve == MIRA_CURVE_BN256 || curve == MIRA_CURVE_GRUMPKIN; }
+static bool field_ok(int field) { return field == MIRA_FIELD_FQ || field == MIRA_FIELD_FR; }
+static Bases *find_bases(uint64_t handle) {                  // null (and the error text) for a handle nobody registered
+    auto it = g_bases.find(handle);
+    if (it == g_bases.end()) { set_error("unknown bases handle"); return nullptr; }
+    return &it->second;
+}
+// Error::TooLongInput (src/commitment.rs:21-24), the reference's text
+static int too_long(size_t len, size_t limit) {
+    set_error("Can't commit too long input: input len: " + std::to_string(len) + ", but limit is " + std::to_string(limit));
+    return MIRA_E_TOO_LONG;
+}
+
+// ------------------------------------------------------------------------------------------
+// MSM: the route is decided in msm_route.hip (on the planner, msm_plan.hip); here it is run
 
 static double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 // One launch sequence through the per-window path (a shared-bucket set included), timed for the width or set trial it belongs
@@ -164,118 +176,46 @@ static int launch_and_report(const Bases &bs, size_t first, const void *d_scalar
     }
     return MIRA_OK;
 }
-// Which of the key's shared-bucket sets a commit goes through: the model's, or -- while the shape's set trial runs (msm_plan.hip:
-// trial_set) -- the set it measures now.  *trial: that trial, or null.
-static const Bases::SharedSet *set_under_trial(const Bases &bs, const Bases::SharedSet *model, size_t n, uint32_t count, bool host_scalars, bool may_trial,
-                                               Bases::WidthTrial **trial) {
-    *trial = (may_trial && bs.shared.size() > 1 && tuned(MIRA_TUNE_TABLE_WIDTH, 0) == 0) ? trial_for(bs, n, count, 4u | (host_scalars ? 2u : 0u), model->c) : nullptr;
-    return *trial ? trial_set(bs, **trial, model) : model;
-}
-
-// The endomorphism copy of a key, built the first time a commit takes the GLV split (msm_plan.hip: glv_possible, choose_glv).  A
-// failed allocation leaves the key as it is.
+// The endomorphism copy of a key, built the first time a commit takes the GLV split (msm_route.h: GlvCopyFn).  A failed allocation
+// leaves the key as it is.
 static bool glv_ready(const Bases &bs) {                     // the copy is there now
     if (bs.glv) return true;
     if (curve_ops(bs.curve).build_glv(const_cast<Bases &>(bs)) != MIRA_OK) { bs.glv_auto_failed = true; (void)rt_last(); return false; }
     return bs.glv != nullptr;
 }
-// sharded: the caller is one rank of a point-chunk sharded MSM.  All ranks must produce the same
-// kind of partial, so the choice between table and per-window mode then depends only on whether
-// the handle has tables (and on the forced width), never on this rank's chunk length.
-// allow_pieces: the caller combines the points itself with horner_pieces (a commit of this process); else the public partial
-// format, one point per window (*shape then has P = 1).
-static int msm_partial_locked(uint64_t handle, size_t first, const void *d_scalars, size_t n, uint64_t *out_partial,
-                              PartialShape *shape, bool sharded = false, int32_t requested_c = 0, const void *h_scalars = nullptr, bool allow_pieces = false) {
+// what mira_msm_last_plan / mira_msm_last_table_bits answer
+static void record_route(const MsmRoute &r) { g.last_c = r.last_c; g.last_w = r.last_w; g.last_table_c = r.last_table_c; }
+
+// A single commit or a partial: the points of its route into out_partial (or rq.windows_dst), their shape into *shape.  h_scalars:
+// the scalars are still in host memory, d_scalars is their staging buffer.
+static int msm_partial_locked(uint64_t handle, MsmRequest rq, const void *d_scalars, const void *h_scalars, uint64_t *out_partial, PartialShape *shape) {
     int rc = ensure_ctx();
     if (rc) return rc;
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    const Bases &bs = it->second;
-    if (first > bs.n || n > bs.n - first) {
-        set_error("Can't commit too long input: input len: " + std::to_string(first + n) + ", but limit is " + std::to_string(bs.n));
-        return MIRA_E_TOO_LONG;
+    const Bases *found = find_bases(handle);
+    if (!found) return MIRA_E_BAD_ARG;
+    const Bases &bs = *found;
+    if (rq.first > bs.n || rq.n > bs.n - rq.first) return too_long(rq.first + rq.n, bs.n);
+    rq.have_scalars = d_scalars != nullptr; rq.host_scalars = h_scalars != nullptr;
+    const MsmRoute r = route_commit(bs, rq, glv_ready);
+    if (r.recorded) {
+        *shape = r.shape;
+        record_route(r);
+        memset(out_partial, 0, MIRA_PARTIAL_U64 * 8);
     }
-    // window width: the call's own (sharded partials), else this key's (mira_msm_set_handle_window_bits), else the process default
-    const int32_t forced_c = bs.forced_c ? bs.forced_c : g.forced_c;
-    // 20- / 22-bit tables pay from 2^18 pairs (2^19 buckets to reduce whatever n is); the shared-bucket sets have the
-    // bucket count of ONE window of the per-window path, so they win from a few thousand pairs.  A key with both
-    // uses the wide tables where they pay and a shared set below.
-    const bool tables_ok = forced_c == 0 && requested_c == 0;
-    const bool table_mode = bs.tables && tables_ok && (sharded || n >= tuned(MIRA_TUNE_TABLE_MIN_N, TABLE_MIN_N));
-    // Data-dependent planning for single (unsharded) commits (ranks of a sharded MSM must agree on
-    // the window width, so they keep the dense estimate).  The statistics are those of the previous
-    // commit of the same length over this key -- successive fold steps commit witnesses of one
-    // shape -- so no call waits for a pre-pass: this call's histogram is enqueued ahead of its MSM
-    // kernels and read after the synchronisation that ends it.
-    const size_t hist_min_n = tuned(MIRA_TUNE_PLAN_HIST_MIN_N, PLAN_HIST_MIN_N);
-    const bool can_hist = !table_mode && !sharded && forced_c == 0 && requested_c == 0 && n >= hist_min_n && d_scalars;
-    // statistics are consumed only by the kind of path that collected them: the halves of the GLV split have other lengths than
-    // the scalars they come from
-    const uint32_t *stat_any = (can_hist && bs.stat_n == n) ? bs.stat_hist : nullptr;
-    const uint32_t *stat_full = bs.stat_kind == 0 ? stat_any : nullptr;
-    const Bases::SharedSet *set = (tables_ok && !table_mode && (sharded || n >= tuned(MIRA_TUNE_SHARED_MIN_N, TABLE16_MIN_N))) ? pick_shared(bs, n, 1, sharded, stat_full) : nullptr;
-    const bool use_hist = can_hist && !set;
-    // a rank of a sharded MSM that was not given a width takes 16, whatever its chunk length: partials
-    // of different widths cannot be combined, and chunk lengths differ between ranks
-    const int32_t width = requested_c ? requested_c : (sharded && forced_c == 0) ? 16 : forced_c;
-    // the GLV split (glv.cuh): 2 n half-length scalars over the interleaved key; not for ranks of a sharded MSM (their partials
-    // must have one shape whatever each rank's key holds) nor beside a table set
-    // (windows wider than 16 bits are for the plain path: a key forced to one, or whose planner picked one, never splits)
-    const MsmPlan p_plain = make_plan(n, width, 1, 0, (use_hist && bs.stat_kind == 0) ? stat_any : nullptr, 256, bs.max_c);
-    const bool glv_ok = !set && !table_mode && !sharded && n != 0 && n < (1ull << 30) && p_plain.c <= MSM_MAX_NARROW_C && glv_possible(bs);
-    const MsmPlan p_split = glv_ok ? make_plan(2 * n, width, 1, 0, (use_hist && bs.stat_kind == 1) ? stat_any : nullptr, GLV_BITS) : p_plain;
-    const bool glv = glv_ok && choose_glv(bs, p_plain, p_split, n) && glv_ready(bs);
-    MsmPlan p = glv ? p_split : p_plain;
-    // the planner's width for this shape, checked against its neighbours on the first commits of the shape (trial_*)
-    // (not before the scalar statistics of the shape exist where they are collected: the model's width for a witness vector
-    // without them is the dense vector's, too far from the best one for its neighbourhood to hold it)
-    const bool stats_pending = use_hist && !stat_any;
-    Bases::WidthTrial *trial = (width == 0 && !sharded && !set && !table_mode && n && !stats_pending) ? trial_for(bs, n, 1, (glv ? 1u : 0u) | (h_scalars ? 2u : 0u), p.c) : nullptr;
-    if (trial && trial_width(*trial) != p.c)
-        p = glv ? make_plan(2 * n, (int32_t)trial_width(*trial), 1, 0, nullptr, GLV_BITS) : make_plan(n, (int32_t)trial_width(*trial), 1, 0, nullptr);
-    p.glv = glv; p.glv_bases = glv ? bs.glv : nullptr;
-    // (a commit of n W >= 2^32 entries is cut into point chunks inside the launch sequence, msm_host.cuh; the 31-bit limit is the
-    // point index of a sorted entry, the sign in bit 31)
-    if (n >= (1ull << 31)) { set_error("n too large for 31-bit point indices"); return MIRA_E_UNSUPPORTED; }
-    if (p.W > MIRA_MAX_WINDOWS) { set_error("window configuration exceeds MIRA_MAX_WINDOWS"); return MIRA_E_UNSUPPORTED; }
-    if (allow_pieces && !g.windows_dst) plan_reduction(p, default_pieces(p, MIRA_MAX_WINDOWS));
-    *shape = PartialShape{p.c, p.W, p.cb, p.pieces};
-    g.last_c = (int32_t)p.c; g.last_w = (int32_t)p.W; g.last_table_c = 0;
-    memset(out_partial, 0, MIRA_PARTIAL_U64 * 8);
-    if (n == 0) {
-        // an empty chunk (a rank beyond the prefix being committed) answers with the identity in the SHAPE its mode has for any
-        // length: the ranks of a sharded MSM exchange and combine partials of one shape (mira_amd/dist.py checks it)
-        if (set) { *shape = PartialShape{0, 1, set->c - 1, 1}; g.last_c = 0; g.last_w = 1; g.last_table_c = (int32_t)set->c; }
-        else if (table_mode) { *shape = PartialShape{0, 64, 0, 1}; g.last_c = 0; g.last_w = 64; g.last_table_c = (int32_t)bs.table_c; }
-        return MIRA_OK;
+    if (r.rc) { set_error(r.err); return r.rc; }
+    if (r.empty) return MIRA_OK;
+    if (r.mode == MSM_WIDE_TABLE) {
+        if (h_scalars) RT_CHECK(rt_h2d(const_cast<void *>(d_scalars), h_scalars, rq.n * 32, g.stream));
+        return curve_ops(bs.curve).msm_launch_table(bs, rq.first, d_scalars, rq.n, out_partial, rq.windows_dst);
     }
-    if (!d_scalars) { set_error("null scalars"); return MIRA_E_BAD_ARG; }
-    // fixed-base mode: window tables present, MSM large enough to be throughput-bound, no forced width
-    if (set) {                                               // shared buckets through the per-window launch sequence
-        Bases::WidthTrial *strial;
-        set = set_under_trial(bs, set, n, 1, h_scalars != nullptr, !sharded && !(can_hist && !stat_any), &strial);
-        MsmPlan ps = make_plan_shared(n, *set, bs.n);
-        if (allow_pieces && !g.windows_dst) plan_reduction(ps, default_pieces(ps, MIRA_MAX_WINDOWS));
-        *shape = PartialShape{0, 1, ps.cb, ps.pieces};       // the pieces of ONE bucket set (P = 1: its sum)
-        g.last_c = 0; g.last_w = (int32_t)ps.pieces; g.last_table_c = (int32_t)set->c;
-        ps.stats = can_hist;
-        return launch_and_report(bs, first, d_scalars, h_scalars, n, ps, out_partial, strial);
-    }
-    if (table_mode) {
-        if (h_scalars) RT_CHECK(rt_h2d(const_cast<void *>(d_scalars), h_scalars, n * 32, g.stream));
-        *shape = PartialShape{0, 64, 0, 1};                 // 64 partial sums, combined by a plain sum
-        g.last_c = 0; g.last_w = 64; g.last_table_c = (int32_t)bs.table_c;
-        return curve_ops(bs.curve).msm_launch_table(bs, first, d_scalars, n, out_partial);
-    }
-    p.stats = use_hist;
-    return launch_and_report(bs, first, d_scalars, h_scalars, n, p, out_partial, trial);
+    return launch_and_report(bs, rq.first, d_scalars, h_scalars, rq.n, r.plan, out_partial, r.trial);
 }
 
 static int combine_locked(int curve, const uint64_t *partials, size_t nparts, uint32_t c, uint32_t W, uint64_t out[8]) {
-    if (curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) { set_error("unknown curve"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve)) { set_error("unknown curve"); return MIRA_E_BAD_ARG; }
     if (!partials || !out || nparts == 0 || c > MSM_MAX_C || W < 1 || W > MIRA_MAX_WINDOWS) { set_error("bad combine arguments"); return MIRA_E_BAD_ARG; }
     std::vector<uint64_t> win((size_t)W * 16);
-    const PartialShape sh{c, W, c ? c - 1 : 0, 1};
+    const PartialShape sh{c, W, c ? c - 1 : 0, 1};           // (a caller's own description of its partials, not a route's)
     on_curve(curve, [&](auto fb, auto) {
         sum_partials<decltype(fb)>(partials, nparts, W, win.data());
         horner_pieces<decltype(fb)>(win.data(), sh, out);
@@ -283,88 +223,43 @@ static int combine_locked(int curve, const uint64_t *partials, size_t nparts, ui
     return MIRA_OK;
 }
 
-
-// count MSMs over the prefix of one key in a single pass of the pipeline (a batch is count * W
-// windows).  Chunked so that the window-counter scan and the 32-bit entry offsets stay in range.
+// count MSMs over the prefix of one key in a single pass of the pipeline (a batch is count * W windows), in the launches its route
+// cuts it into.  h_batch: the vectors are still in host memory, d_scalars is their staging buffer.
 static int msm_batch_device_locked(uint64_t handle, const void *d_scalars, size_t n, size_t count, size_t stride, uint64_t *out_affine,
-                                   const uint64_t *const *h_batch = nullptr /* the vectors are still in host memory: d_scalars is their staging buffer */) {
+                                   const uint64_t *const *h_batch = nullptr) {
     int rc = ensure_ctx();
     if (rc) return rc;
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    const Bases &bs = it->second;
+    const Bases *found = find_bases(handle);
+    if (!found) return MIRA_E_BAD_ARG;
+    const Bases &bs = *found;
     if (!out_affine || (count && n && !d_scalars) || (count > 1 && stride < n)) { set_error("bad batch arguments"); return MIRA_E_BAD_ARG; }
-    if (n > bs.n) {
-        set_error("Can't commit too long input: input len: " + std::to_string(n) + ", but limit is " + std::to_string(bs.n));
-        return MIRA_E_TOO_LONG;
-    }
-    if (n == 0) { memset(out_affine, 0, count * 64); return MIRA_OK; }
-    if (n >= (1ull << 31)) { set_error("n too large for 32-bit entry offsets"); return MIRA_E_UNSUPPORTED; }
-    // shared-bucket tables: every commitment of the batch gets ONE bucket set for its W windows
-    // (ceil(256 / c) additions per pair, 2^(c-1) buckets per commitment instead of W 2^(c-1)),
-    // and its partial sums come back to be added -- no chain of doublings
-    const int32_t forced_c = bs.forced_c ? bs.forced_c : g.forced_c;
-    const Bases::SharedSet *set = (forced_c == 0 && n >= tuned(MIRA_TUNE_SHARED_MIN_N, TABLE16_MIN_N)) ? pick_shared(bs, n, (uint32_t)std::min<size_t>(count, 64), false) : nullptr;
-    if (set) {
-        // which of the key's sets: the model's choice, checked against the others on the first batches of the shape (trial_report_sets)
-        Bases::WidthTrial *strial;
-        set = set_under_trial(bs, set, n, (uint32_t)count, h_batch != nullptr, count <= 64, &strial);
-        const auto t_set = std::chrono::steady_clock::now();
-        const uint32_t Ws = (256 + set->c - 1) / set->c;
-        const size_t per = std::max<size_t>(1, std::min<size_t>(64, (size_t)(((1ull << 32) - 1) / ((uint64_t)n * Ws))));
-        std::vector<uint64_t> sums;
-        for (size_t done = 0; done < count; done += per) {
-            const size_t cnt = std::min(per, count - done);
-            MsmPlan p = make_plan_shared(n, *set, bs.n, (uint32_t)cnt, stride);
-            plan_reduction(p, default_pieces(p, MIRA_MAX_WINDOWS));
-            p.h_batch = h_batch ? h_batch + done : nullptr;
-            g.last_c = 0; g.last_w = (int32_t)p.pieces; g.last_table_c = (int32_t)set->c;
-            sums.assign(cnt * p.pieces * 16, 0);
-            const unsigned char *sc = reinterpret_cast<const unsigned char *>(d_scalars) + done * stride * 32;
-            rc = curve_ops(bs.curve).msm_launch(bs, 0, sc, nullptr, n, p, sums.data());
-            if (rc) return rc;
-            const PartialShape sh{0, 1, p.cb, p.pieces};
-            on_curve(bs.curve, [&](auto fb, auto) {
-                for (size_t b = 0; b < cnt; b++) horner_pieces<decltype(fb)>(sums.data() + b * p.pieces * 16, sh, out_affine + (done + b) * 8);
-            });
-        }
-        if (strial) trial_report(*strial, us_since(t_set), bs);   // (the whole batch: its chunks and their epilogues)
-        return MIRA_OK;
-    }
-    // the GLV split (glv.cuh) where the key has its endomorphism copy: 2 n half-length scalars per commitment, half the windows
-    bool glv = n < (1ull << 30) && (forced_c == 0 || forced_c <= (int32_t)MSM_MAX_NARROW_C) && glv_possible(bs);
-    if (glv) {                                               // the planners' estimates for a batch of this shape decide (choose_glv)
-        const uint32_t shape = (uint32_t)std::min<size_t>(count, 8);
-        const MsmPlan plain = make_batch_plan(n, forced_c, shape, stride, 256, bs.max_c);
-        glv = plain.c <= MSM_MAX_NARROW_C && choose_glv(bs, plain, make_plan(2 * n, forced_c, shape, stride, nullptr, GLV_BITS), n * shape) && glv_ready(bs);
-    }
-    const size_t nv = glv ? 2 * n : n;
-    const uint32_t bits = glv ? GLV_BITS : 256;
-    const uint32_t cmax = glv ? MSM_MAX_NARROW_C : bs.max_c;
-    const size_t per = batch_per_launch(nv, forced_c, bits, cmax);
-    std::vector<uint64_t> win;
-    for (size_t done = 0; done < count; done += per) {
-        const size_t cnt = std::min(per, count - done);
-        MsmPlan p = make_batch_plan(nv, forced_c, (uint32_t)cnt, stride, bits, cmax);
-        Bases::WidthTrial *trial = forced_c == 0 ? trial_for(bs, n, (uint32_t)cnt, (glv ? 1u : 0u) | (h_batch ? 2u : 0u), p.c) : nullptr;
-        if (trial && trial_width(*trial) != p.c && (uint64_t)((bits + trial_width(*trial) - 1) / trial_width(*trial)) * cnt * (1ull << (trial_width(*trial) - 1)) <= SCAN_MAX_COUNTERS)
-            p = make_plan(nv, (int32_t)trial_width(*trial), (uint32_t)cnt, stride, nullptr, bits);      // (a width whose counters one scan takes)
-        p.glv = glv; p.glv_bases = glv ? bs.glv : nullptr;
-        p.h_batch = h_batch ? h_batch + done : nullptr;
-        plan_reduction(p, default_pieces(p, 1u << 20));
-        g.last_c = (int32_t)p.c; g.last_w = (int32_t)p.W; g.last_table_c = 0;
-        win.assign((size_t)p.Wt * p.pieces * 16, 0);
+    if (n > bs.n) return too_long(n, bs.n);
+    MsmRequest rq;
+    rq.n = n; rq.count = count; rq.stride = stride; rq.have_scalars = d_scalars != nullptr; rq.h_batch = h_batch;
+    const BatchRoute b = route_batch(bs, rq, glv_ready);
+    if (b.rc) { set_error(b.err); return b.rc; }
+    if (b.empty) { memset(out_affine, 0, count * 64); return MIRA_OK; }
+    const auto t_batch = std::chrono::steady_clock::now();
+    std::vector<uint64_t> pts;
+    for (size_t done = 0; done < count; done += b.per) {
+        const MsmRoute r = route_batch_launch(bs, rq, b, done);
+        const MsmPlan &p = r.plan;
+        record_route(r);
+        pts.assign((size_t)p.nsets * p.pieces * 16, 0);
         const unsigned char *sc = reinterpret_cast<const unsigned char *>(d_scalars) + done * stride * 32;
-        const bool measured = trial && trial_width(*trial) == p.c;
-        rc = launch_and_report(bs, 0, sc, nullptr, n, p, win.data(), measured ? trial : nullptr);
+        rc = launch_and_report(bs, 0, sc, nullptr, n, p, pts.data(), r.trial);
         if (rc) return rc;
-        if (trial && !measured) trial->done = true;          // the candidate does not fit one scan: the walk ends where it is
-        // the epilogues of a batch are independent chains of ~250 doublings (60 us each): one host thread per commitment
-        const PartialShape sh{p.c, p.W, p.cb, p.pieces};
+        if (r.trial_to_end) r.trial_to_end->done = true;
+        const size_t per_commit = (size_t)r.shape.W * r.shape.P * 16;
         on_curve(bs.curve, [&](auto fb, auto) {
-            host_parallel_for(cnt, [&](size_t b) { horner_pieces<decltype(fb)>(win.data() + b * p.W * p.pieces * 16, sh, out_affine + (done + b) * 8); });
+            auto finish = [&](size_t i) { horner_pieces<decltype(fb)>(pts.data() + i * per_commit, r.shape, out_affine + (done + i) * 8); };
+            // the per-window epilogues of a batch are independent chains of ~250 doublings (60 us each): one host thread per
+            // commitment; the sums of a shared-bucket set are just added
+            if (r.mode == MSM_PER_WINDOW) host_parallel_for(p.count, finish);
+            else for (size_t i = 0; i < p.count; i++) finish(i);
         });
     }
+    if (b.set_trial) trial_report(*b.set_trial, us_since(t_batch), bs);   // (the whole batch: its launches and their epilogues)
     return MIRA_OK;
 }
 
@@ -430,7 +325,7 @@ const char *mira_last_error(void) { return g_err.c_str(); }
 static int register_common(int curve, const void *src, bool src_on_device, size_t n, uint64_t *handle_out) {
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || !handle_out || (n && !src)) { set_error("bad register arguments"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve) || !handle_out || (n && !src)) { set_error("bad register arguments"); return MIRA_E_BAD_ARG; }
     Bases b; b.curve = curve; b.n = n; b.owned = true;
     if (rt_malloc(&b.d, std::max<size_t>(64, n * 64)) != hipSuccess || !b.d) { set_error("device allocation for bases failed"); return MIRA_E_ALLOC; }
     if (n) {
@@ -456,21 +351,21 @@ int mira_msm_register_bases_device(int curve, const void *d_bases, size_t n, uin
 }
 int mira_msm_unregister(uint64_t handle) {
     std::lock_guard<std::mutex> lk(g_lock);
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    if (it->second.owned && it->second.d) (void)rt_free(it->second.d);
-    if (it->second.tables) (void)rt_free(it->second.tables);
-    for (auto &set : it->second.shared) (void)rt_free(set.p);
-    if (it->second.glv) (void)rt_free(it->second.glv);
-    g_bases.erase(it);
+    const Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    if (bs->owned && bs->d) (void)rt_free(bs->d);
+    if (bs->tables) (void)rt_free(bs->tables);
+    for (auto &set : bs->shared) (void)rt_free(set.p);
+    if (bs->glv) (void)rt_free(bs->glv);
+    g_bases.erase(g_bases.find(handle));
     return MIRA_OK;
 }
 static int precompute_locked(uint64_t handle, int32_t window_bits) {
     int rc = ensure_ctx();
     if (rc) return rc;
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    Bases &bs = it->second;
+    Bases *found = find_bases(handle);
+    if (!found) return MIRA_E_BAD_ARG;
+    Bases &bs = *found;
     if (window_bits >= 8 && window_bits <= 16) {             // a shared-bucket set: any number of widths beside each other
         for (const auto &set : bs.shared) if (set.c == (uint32_t)window_bits) return MIRA_OK;
         const uint32_t W = (256 + (uint32_t)window_bits - 1) / (uint32_t)window_bits;
@@ -504,9 +399,9 @@ int mira_msm_check_bases(uint64_t handle) {
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    const Bases &bs = it->second;
+    const Bases *found = find_bases(handle);
+    if (!found) return MIRA_E_BAD_ARG;
+    const Bases &bs = *found;
     if (bs.n == 0) return MIRA_OK;
     if ((rc = g.heavy.ensure(64))) return rc;
     uint32_t *bad = reinterpret_cast<uint32_t *>(g.heavy.p);
@@ -523,7 +418,9 @@ static int msm_device_locked(uint64_t handle, const void *d_scalars, size_t n, u
     if (!out_affine) { set_error("null output"); return MIRA_E_BAD_ARG; }
     uint64_t part[MIRA_PARTIAL_U64];
     PartialShape sh;
-    int rc = msm_partial_locked(handle, 0, d_scalars, n, part, &sh, false, 0, h_scalars, true);
+    MsmRequest rq;
+    rq.n = n; rq.caller_combines = true;
+    int rc = msm_partial_locked(handle, rq, d_scalars, h_scalars, part, &sh);
     if (rc) return rc;
     on_curve(g_bases[handle].curve, [&](auto fb, auto) { horner_pieces<decltype(fb)>(part, sh, out_affine); });
     return MIRA_OK;
@@ -537,12 +434,9 @@ int mira_msm(uint64_t handle, const uint64_t *scalars, size_t n, uint64_t out_af
     int rc = ensure_ctx();
     if (rc) return rc;
     if (n && !scalars) { set_error("null scalars"); return MIRA_E_BAD_ARG; }
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    if (n > it->second.n) {   // length check before any copy, as commit does (src/commitment.rs:79)
-        set_error("Can't commit too long input: input len: " + std::to_string(n) + ", but limit is " + std::to_string(it->second.n));
-        return MIRA_E_TOO_LONG;
-    }
+    const Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    if (n > bs->n) return too_long(n, bs->n);   // length check before any copy, as commit does (src/commitment.rs:79)
     // the scalars cross PCIe inside the launch sequence, chunk by chunk beside the kernels (msm_host.cuh)
     if (n && (rc = g.scalars_stage.ensure(n * 32))) return rc;
     return msm_device_locked(handle, g.scalars_stage.p, n, out_affine, n ? scalars : nullptr);
@@ -556,12 +450,9 @@ int mira_msm_batch(uint64_t handle, const uint64_t *const *scalars, size_t n, si
     int rc = ensure_ctx();
     if (rc) return rc;
     if (count && n && !scalars) { set_error("null scalars"); return MIRA_E_BAD_ARG; }
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    if (n > it->second.n) {
-        set_error("Can't commit too long input: input len: " + std::to_string(n) + ", but limit is " + std::to_string(it->second.n));
-        return MIRA_E_TOO_LONG;
-    }
+    const Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    if (n > bs->n) return too_long(n, bs->n);
     if (n && count) {
         if ((rc = g.scalars_stage.ensure(n * count * 32))) return rc;
         for (size_t b = 0; b < count; b++)
@@ -576,7 +467,9 @@ int mira_msm_partial_device(uint64_t handle, size_t first, const void *d_scalars
     if (!out_partial || !window_bits || !num_windows) { set_error("null output"); return MIRA_E_BAD_ARG; }
     if (*window_bits != 0 && (*window_bits < 4 || *window_bits > (int32_t)MSM_MAX_C)) { set_error("window_bits must be 0 or 4..20"); return MIRA_E_BAD_ARG; }
     PartialShape sh;
-    int rc = msm_partial_locked(handle, first, d_scalars, n, out_partial, &sh, true, *window_bits);
+    MsmRequest rq;
+    rq.first = first; rq.n = n; rq.sharded = true; rq.requested_c = *window_bits;
+    int rc = msm_partial_locked(handle, rq, d_scalars, nullptr, out_partial, &sh);
     if (rc) return rc;
     *window_bits = (int32_t)sh.c; *num_windows = (int32_t)sh.W;
     return MIRA_OK;
@@ -619,17 +512,17 @@ int mira_msm_set_window_bits(int32_t c) {
 int mira_msm_set_handle_window_bits(uint64_t handle, int32_t c) {
     std::lock_guard<std::mutex> lk(g_lock);
     if (c != 0 && (c < 4 || c > (int32_t)MSM_MAX_C)) { set_error("window bits must be 0 or in [4,20]"); return MIRA_E_BAD_ARG; }
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    it->second.forced_c = c;
+    Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    bs->forced_c = c;
     return MIRA_OK;
 }
 int mira_msm_set_handle_max_window_bits(uint64_t handle, int32_t cmax) {
     std::lock_guard<std::mutex> lk(g_lock);
     if (cmax < (int32_t)MSM_MAX_NARROW_C || cmax > (int32_t)MSM_MAX_C) { set_error("max window bits must be in [16,20]"); return MIRA_E_BAD_ARG; }
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    if (it->second.max_c != (uint32_t)cmax) { it->second.max_c = (uint32_t)cmax; it->second.trials.clear(); }   // the width trials start again
+    Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    if (bs->max_c != (uint32_t)cmax) { bs->max_c = (uint32_t)cmax; bs->trials.clear(); }   // the width trials start again
     return MIRA_OK;
 }
 int mira_msm_partial_to_device(uint64_t handle, size_t first, const void *d_scalars, size_t n, void *d_out_partial,
@@ -643,10 +536,9 @@ int mira_msm_partial_to_device(uint64_t handle, size_t first, const void *d_scal
     RT_CHECK(rt_sync(g.stream));
     uint64_t unused[MIRA_PARTIAL_U64];
     PartialShape sh;
-    g.windows_dst = d_out_partial;
-    rc = msm_partial_locked(handle, first, d_scalars, n, unused, &sh, true, *window_bits);
-    g.windows_dst = nullptr;
-    if (rc) return rc;
+    MsmRequest rq;
+    rq.first = first; rq.n = n; rq.sharded = true; rq.requested_c = *window_bits; rq.windows_dst = d_out_partial;
+    if ((rc = msm_partial_locked(handle, rq, d_scalars, nullptr, unused, &sh))) return rc;
     *window_bits = (int32_t)sh.c; *num_windows = (int32_t)sh.W;
     return MIRA_OK;
 }
@@ -656,7 +548,7 @@ int mira_msm_register_bases_file(int curve, const char *path, uint32_t k, int va
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || !path || !handle_out || k > 31) { set_error("bad register arguments"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve) || !path || !handle_out || k > 31) { set_error("bad register arguments"); return MIRA_E_BAD_ARG; }
     const size_t n = (size_t)1 << k;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) { set_error(std::string(path) + ": " + strerror(errno)); return MIRA_E_IO; }
@@ -689,11 +581,11 @@ int mira_msm_save_bases_file(uint64_t handle, const char *path) {
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end() || !path) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
+    const Bases *bs = find_bases(handle);
+    if (!bs || !path) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
     const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) { set_error(std::string(path) + ": " + strerror(errno)); return MIRA_E_IO; }
-    rc = curve_ops(it->second.curve).save_bases_file(it->second, fd);
+    rc = curve_ops(bs->curve).save_bases_file(*bs, fd);
     if (close(fd) != 0 && rc == MIRA_OK) { set_error(std::string("close failed: ") + strerror(errno)); rc = MIRA_E_IO; }
     return rc;
 }
@@ -764,17 +656,22 @@ int mira_fold_witness_device(int field, void *d_out, const void *d_w1, const voi
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != 0 && field != 1) || !r || (n && (!d_out || !d_w1 || !d_w2))) { set_error("bad fold arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !r || (n && (!d_out || !d_w1 || !d_w2))) { set_error("bad fold arguments"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
     return fold_witness_device(field, d_out, d_w1, d_w2, r, n);
+}
+// every cross-term vector of a fold over n elements is there
+static int check_cross_terms(const void *const *d_cross_terms, size_t num_terms, size_t n) {
+    for (size_t k = 0; k < num_terms; k++)
+        if (n && !d_cross_terms[k]) { set_error("null cross term"); return MIRA_E_BAD_ARG; }
+    return MIRA_OK;
 }
 int mira_fold_error_device(int field, void *d_e, const void *const *d_cross_terms, size_t num_terms, const uint64_t r[4], size_t n) {
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != 0 && field != 1) || !r || num_terms > 16 || (num_terms && !d_cross_terms) || (n && !d_e)) { set_error("bad fold arguments"); return MIRA_E_BAD_ARG; }
-    for (size_t k = 0; k < num_terms; k++)
-        if (n && !d_cross_terms[k]) { set_error("null cross term"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !r || num_terms > 16 || (num_terms && !d_cross_terms) || (n && !d_e)) { set_error("bad fold arguments"); return MIRA_E_BAD_ARG; }
+    if ((rc = check_cross_terms(d_cross_terms, num_terms, n))) return rc;
     if (!n || !num_terms) return MIRA_OK;
     return fold_error_device(field, d_e, d_cross_terms, num_terms, r, n);
 }
@@ -783,17 +680,15 @@ int mira_fold_relaxed_witness_device(int field, void *d_w_out, const void *d_w1,
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != 0 && field != 1) || !r || num_terms > 16 || (num_terms && !d_cross_terms) || (n_w && (!d_w_out || !d_w1 || !d_w2)) || (n && (!d_e_out || !d_e))) {
+    if (!field_ok(field) || !r || num_terms > 16 || (num_terms && !d_cross_terms) || (n_w && (!d_w_out || !d_w1 || !d_w2)) || (n && (!d_e_out || !d_e))) {
         set_error("bad fold arguments");
         return MIRA_E_BAD_ARG;
     }
-    for (size_t k = 0; k < num_terms; k++)
-        if (n && !d_cross_terms[k]) { set_error("null cross term"); return MIRA_E_BAD_ARG; }
+    if ((rc = check_cross_terms(d_cross_terms, num_terms, n))) return rc;
     if (!n_w && !n) return MIRA_OK;
     return fold_relaxed_device(field, d_w_out, d_w1, d_w2, n_w, d_e_out, d_e, d_cross_terms, num_terms, r, n);
 }
 // ---- lookup argument (lookup.hip)
-static bool lk_field_ok(int field) { return field == MIRA_FIELD_FQ || field == MIRA_FIELD_FR; }
 // [a, a + 32 na) and [b, b + 32 nb) share a byte
 static bool lk_overlap(const void *a, size_t na, const void *b, size_t nb) {
     if (!na || !nb) return false;
@@ -808,7 +703,7 @@ int mira_batch_invert_device(int field, void *d_out, const void *d_in, size_t n)
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if (!lk_field_ok(field) || (n && (!d_out || !d_in))) { set_error("bad batch-inversion arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || (n && (!d_out || !d_in))) { set_error("bad batch-inversion arguments"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
     if ((rc = lk_check_len(n))) return rc;
     if (d_out != d_in && lk_overlap(d_out, n, d_in, n)) { set_error("the output overlaps the input (only d_out == d_in is allowed)"); return MIRA_E_BAD_ARG; }
@@ -818,7 +713,7 @@ int mira_lookup_m_device(int field, void *d_m, const void *d_l, size_t n_l, cons
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if (!lk_field_ok(field) || (n_t && (!d_m || !d_t)) || (n_l && n_t && !d_l)) { set_error("bad lookup_m arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || (n_t && (!d_m || !d_t)) || (n_l && n_t && !d_l)) { set_error("bad lookup_m arguments"); return MIRA_E_BAD_ARG; }
     if (!n_t) return MIRA_OK;
     if ((rc = lk_check_len(n_l)) || (rc = lk_check_len(n_t))) return rc;
     if (lk_overlap(d_m, n_t, d_t, n_t) || lk_overlap(d_m, n_t, d_l, n_l)) { set_error("m overlaps an input"); return MIRA_E_BAD_ARG; }
@@ -828,7 +723,7 @@ int mira_lookup_h_g_device(int field, void *d_h, void *d_g, const void *d_l, siz
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if (!lk_field_ok(field) || !r || (n_l && (!d_h || !d_l)) || (n_t && (!d_g || !d_t || !d_m))) { set_error("bad lookup_h_g arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !r || (n_l && (!d_h || !d_l)) || (n_t && (!d_g || !d_t || !d_m))) { set_error("bad lookup_h_g arguments"); return MIRA_E_BAD_ARG; }
     if (!n_l && !n_t) return MIRA_OK;
     if ((rc = lk_check_len(n_l)) || (rc = lk_check_len(n_t))) return rc;
     const void *ins[3] = {d_l, d_t, d_m};
@@ -851,7 +746,7 @@ int mira_count_ne_device(int field, const void *d_a, const void *d_b, size_t n, 
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if (!lk_field_ok(field) || !count_out || (n && !d_a)) { set_error("bad count_ne arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !count_out || (n && !d_a)) { set_error("bad count_ne arguments"); return MIRA_E_BAD_ARG; }
     if (!n) { *count_out = 0; if (first_out) *first_out = UINT64_MAX; return MIRA_OK; }
     return count_ne_device(field, d_a, d_b, n, count_out, first_out);
 }
@@ -859,7 +754,7 @@ int mira_sum_sub_device(int field, const void *d_a, const void *d_b, size_t n, u
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if (!lk_field_ok(field) || !out || (n && !d_a)) { set_error("bad sum_sub arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !out || (n && !d_a)) { set_error("bad sum_sub arguments"); return MIRA_E_BAD_ARG; }
     if (!n) { memset(out, 0, 32); return MIRA_OK; }
     return sum_sub_device(field, d_a, d_b, n, out);
 }
@@ -881,7 +776,7 @@ int mira_perm_compile(int field, const uint64_t *rows, const uint64_t *cols, con
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if (!lk_field_ok(field) || !handle_out || (nnz && (!rows || !cols))) { set_error("bad permutation matrix arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !handle_out || (nnz && (!rows || !cols))) { set_error("bad permutation matrix arguments"); return MIRA_E_BAD_ARG; }
     if ((uint64_t)n >= (1ull << 32) || (uint64_t)nnz >= (1ull << 32)) { set_error("permutation matrices of 2^32 rows or entries or more are not supported"); return MIRA_E_UNSUPPORTED; }
     return perm_compile(field, rows, cols, values, nnz, n, handle_out);
 }
@@ -902,7 +797,7 @@ int mira_lincomb_device(int field, void *d_out, const void *const *d_vecs, const
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != MIRA_FIELD_FQ && field != MIRA_FIELD_FR) || num_vecs == 0 || num_vecs > 16 || !d_vecs || !coeffs || (n && !d_out)) { set_error("bad linear-combination arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || num_vecs == 0 || num_vecs > 16 || !d_vecs || !coeffs || (n && !d_out)) { set_error("bad linear-combination arguments"); return MIRA_E_BAD_ARG; }
     for (size_t k = 0; k < num_vecs; k++)
         if (n && !d_vecs[k]) { set_error("null vector"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
@@ -912,7 +807,7 @@ int mira_lincomb_multi_device(int field, void *const *d_outs, size_t num_outs, c
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != MIRA_FIELD_FQ && field != MIRA_FIELD_FR) || num_outs == 0 || num_outs > 8 || num_vecs == 0 || num_vecs > 16 || !d_outs || !d_vecs || !coeffs) {
+    if (!field_ok(field) || num_outs == 0 || num_outs > 8 || num_vecs == 0 || num_vecs > 16 || !d_outs || !d_vecs || !coeffs) {
         set_error("bad linear-combination arguments");
         return MIRA_E_BAD_ARG;
     }
@@ -932,7 +827,7 @@ int mira_pow_tree_reduce_device(int field, const void *d_leaves, size_t n_leaves
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != MIRA_FIELD_FQ && field != MIRA_FIELD_FR) || !d_leaves || !out || num_points == 0 || num_points > 65535 || n_leaves == 0) { set_error("bad tree-reduction arguments"); return MIRA_E_BAD_ARG; }
+    if (!field_ok(field) || !d_leaves || !out || num_points == 0 || num_points > 65535 || n_leaves == 0) { set_error("bad tree-reduction arguments"); return MIRA_E_BAD_ARG; }
     if (n_leaves & (n_leaves - 1)) {
         // itertools::tree_reduce would pair nodes of different heights: `unreachable!` in the reference
         set_error("tree reduction needs a power-of-two number of leaves, got " + std::to_string(n_leaves));
@@ -944,14 +839,17 @@ int mira_pow_tree_reduce_device(int field, const void *d_leaves, size_t n_leaves
     if (leaf_point_stride != 0 && leaf_point_stride < n_leaves) { set_error("leaf_point_stride shorter than the leaves"); return MIRA_E_BAD_ARG; }
     return pow_tree_reduce_device(field, d_leaves, levels, leaf_point_stride, weights, num_points, out);
 }
+// a cross-term graph as an entry point may be handed it: its arrays are there where it counts some, and the counts are in range
+static bool graph_args_ok(int field, const mira_graph *graph, uint32_t num_columns) {
+    return field_ok(field) && graph && !(graph->code_words && !graph->code) && !(graph->num_constants && !graph->constants) &&
+           !(graph->num_rotations && !graph->rotations) && num_columns <= 0xFFFFFu && graph->num_rotations <= 512u;
+}
 int mira_graph_eval_device(int field, const mira_graph *graph, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges,
                            uint32_t num_challenges, size_t num_rows, void *d_out) {
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != MIRA_FIELD_FQ && field != MIRA_FIELD_FR) || !graph || (graph->code_words && !graph->code) || (graph->num_constants && !graph->constants) ||
-        (graph->num_rotations && !graph->rotations) || (num_columns && !columns) || (num_challenges && !challenges) || (num_rows && !d_out) ||
-        num_columns > 0xFFFFFu || graph->num_rotations > 512u) {
+    if (!graph_args_ok(field, graph, num_columns) || (num_columns && !columns) || (num_challenges && !challenges) || (num_rows && !d_out)) {
         set_error("bad graph evaluation arguments");
         return MIRA_E_BAD_ARG;
     }
@@ -961,8 +859,7 @@ int mira_graph_compile(int field, const mira_graph *graph, uint32_t num_challeng
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((field != MIRA_FIELD_FQ && field != MIRA_FIELD_FR) || !graph || !handle_out || (graph->code_words && !graph->code) || (graph->num_constants && !graph->constants) ||
-        (graph->num_rotations && !graph->rotations) || num_columns > 0xFFFFFu || graph->num_rotations > 512u) {
+    if (!graph_args_ok(field, graph, num_columns) || !handle_out) {
         set_error("bad graph compilation arguments");
         return MIRA_E_BAD_ARG;
     }
@@ -1016,18 +913,18 @@ int mira_graph_jit_source(uint64_t handle, const mira_eval_column *columns, uint
     return graph_jit_source(handle, columns, num_columns, buf, cap, len_out);
 }
 int mira_g1_mul_add(int curve, const uint64_t acc[8], const uint64_t scalar[4], const uint64_t point[8], uint64_t out[8]) {
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || !acc || !scalar || !point || !out) { set_error("bad arguments"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve) || !acc || !scalar || !point || !out) { set_error("bad arguments"); return MIRA_E_BAD_ARG; }
     on_curve(curve, [&](auto fb, auto fs) { g1_mul_add_t<decltype(fb), decltype(fs)>(acc, scalar, point, out); });
     return MIRA_OK;
 }
 int mira_g1_lincomb(int curve, const uint64_t acc[8], const uint64_t *scalars, const uint64_t *points, size_t count, uint64_t out[8]) {
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || !acc || !out || (count && (!scalars || !points)) || count > 64) { set_error("bad arguments"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve) || !acc || !out || (count && (!scalars || !points)) || count > 64) { set_error("bad arguments"); return MIRA_E_BAD_ARG; }
     on_curve(curve, [&](auto fb, auto fs) { g1_lincomb_t<decltype(fb), decltype(fs)>(acc, scalars, points, count, out); });
     return MIRA_OK;
 }
 int mira_g1_fold_commitments(int curve, const uint64_t r[4], const uint64_t *w1, const uint64_t *w2, size_t nw, const uint64_t e[8], const uint64_t *t_commits,
                              size_t count, uint64_t *w_out, uint64_t e_out[8]) {
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || !r || !e || !e_out || (nw && (!w1 || !w2 || !w_out)) || (count && !t_commits) || nw > 64 || count > 64) {
+    if (!curve_ok(curve) || !r || !e || !e_out || (nw && (!w1 || !w2 || !w_out)) || (count && !t_commits) || nw > 64 || count > 64) {
         set_error("bad arguments");
         return MIRA_E_BAD_ARG;
     }
@@ -1038,9 +935,9 @@ int mira_msm_download_bases(uint64_t handle, size_t first, size_t n, uint64_t *b
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    auto it = g_bases.find(handle);
-    if (it == g_bases.end()) { set_error("unknown bases handle"); return MIRA_E_BAD_ARG; }
-    const Bases &bs = it->second;
+    const Bases *found = find_bases(handle);
+    if (!found) return MIRA_E_BAD_ARG;
+    const Bases &bs = *found;
     if (first > bs.n || n > bs.n - first || (n && !bases_out)) { set_error("range outside the registered key"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
     if ((rc = g.scalars_stage.ensure(n * 64))) return rc;
@@ -1054,7 +951,7 @@ int mira_synth_scalars_device(int curve, size_t n, uint64_t index0, uint64_t see
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || (n && !d_out)) { set_error("bad synth arguments"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve) || (n && !d_out)) { set_error("bad synth arguments"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
     return curve_ops(curve).synth_scalars(n, index0, seed, kind, d_out);
 }
@@ -1062,7 +959,7 @@ int mira_synth_bases_device(int curve, size_t n, uint64_t index0, uint64_t seed,
     std::lock_guard<std::mutex> lk(g_lock);
     int rc = ensure_ctx();
     if (rc) return rc;
-    if ((curve != MIRA_CURVE_BN256 && curve != MIRA_CURVE_GRUMPKIN) || (n && !d_out)) { set_error("bad synth arguments"); return MIRA_E_BAD_ARG; }
+    if (!curve_ok(curve) || (n && !d_out)) { set_error("bad synth arguments"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
     return curve_ops(curve).synth_bases(n, index0, seed, d_out);
 }

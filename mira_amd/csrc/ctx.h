@@ -138,7 +138,6 @@ struct Ctx {
     uint32_t hist_sel = 0;           // which of the two device histograms the next commit adds into
     unsigned char *out_host = nullptr, *out_host_dev = nullptr; size_t out_host_cap = 0;   // mapped pinned memory: k_set_finish writes the pieces + statistics + a flag word there
     uint64_t out_stamp = 0; DevBuf finish_ctr;   // cross-term evaluator: staged program, intermediates[slot][lane]
-    void *windows_dst = nullptr;     // mira_msm_partial_to_device: device destination of the window sums of the call in flight
     uint64_t next_handle = 1;
 };
 extern Ctx g;
@@ -215,6 +214,7 @@ struct MsmPlan {
     // a batch whose vectors are still in HOST memory (mira_msm_batch): h_batch[b] = vector b; they cross PCIe in point chunks beside
     // the kernels, chunk k staged as count consecutive slices of its length (the stride of the digit kernel is then the chunk's)
     const uint64_t *const *h_batch = nullptr;
+    void *windows_dst = nullptr;   // mira_msm_partial_to_device: the window sums stay in device memory, here (else they come back to the host)
     // bucket reduction (reduce_kernels.cuh, plan_reduction below): nsets bucket sets of 2^cb buckets each, chunks of 2^lambda
     // buckets, 2^kappa chunks per workgroup, 2^gamma workgroup nodes per set, `pieces` results per set; rquad: phase A by quads
     uint32_t nsets = 0, cb = 0, lambda = 0, kappa = 0, gamma = 0, pieces = 1;
@@ -267,7 +267,8 @@ struct CurveOps {
     int (*init)();
     // h_scalars != null: the scalars are still in host memory; d_scalars is then the device staging buffer they are copied to
     int (*msm_launch)(const Bases &bs, size_t first, const void *d_scalars, const void *h_scalars, size_t n, const MsmPlan &p, uint64_t *host_windows);
-    int (*msm_launch_table)(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums);
+    // d_sums_dst != null: the sums stay in device memory, there (as MsmPlan::windows_dst)
+    int (*msm_launch_table)(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums, void *d_sums_dst);
     int (*build_tables)(Bases &bs, uint32_t c, uint32_t W);
     int (*build_glv)(Bases &bs);
     int (*convert_bases)(const void *d_src, void *d_dst, size_t n);

@@ -321,12 +321,12 @@ static int msm_launch_body(const Bases &bs, size_t first, const void *d_scalars,
     tm_mark("reduce_chunks");
     uint32_t *no_ctr = nullptr;
     uint64_t *no_flag = nullptr;
-    if (g.windows_dst) {                                     // mira_msm_partial_to_device: the sums stay in device memory
+    if (p.windows_dst) {                                     // mira_msm_partial_to_device: the sums stay in device memory
         LAUNCH_BARRIER(k_set_finish<F>, p.nsets, SET_FINISH_BLOCK, lds_b, st, reinterpret_cast<const unsigned char *>(g.chunks.p), p.kappa + 2, p.gamma, p.lambda, pc,
                        reinterpret_cast<unsigned char *>(g.window_sums.p), (const uint32_t *)hist, no_ctr, no_flag, (uint64_t)0);
         tm_mark("window_sum");
         RT_CHECK(rt_last());
-        RT_CHECK(rt_d2d(g.windows_dst, g.window_sums.p, (size_t)npts * 128, st));
+        RT_CHECK(rt_d2d(p.windows_dst, g.window_sums.p, (size_t)npts * 128, st));
         RT_CHECK(rt_sync(st));
     } else {
         // pieces (and statistics) straight into mapped pinned memory, a flag word behind them: no copy command, no
@@ -453,7 +453,7 @@ template <class F> static int build_tables(Bases &bs, uint32_t c, uint32_t W) {
 // One MSM over the tables: W signed c-bit digits per scalar (c = 20: 13, c = 22: 12), one set of 2^(c-1)
 // buckets.  Returns TABLE_SUMS partial sums (XYZZ, canonical, reference form) whose plain sum is the result.
 template <class F, class FS>
-static int msm_launch_table(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums) {
+static int msm_launch_table(const Bases &bs, size_t first, const void *d_scalars, size_t n, uint64_t *host_sums, void *d_sums_dst) {
     int rc;
     const TableCfg tc = table_cfg(bs.table_c);
     const uint32_t TABLE_W = tc.W, TABLE_B = tc.B, TABLE_FINE_BITS = tc.fine_bits;
@@ -544,7 +544,7 @@ static int msm_launch_table(const Bases &bs, size_t first, const void *d_scalars
                    reinterpret_cast<const unsigned char *>(g.chunks.p), nchunks / TABLE_SUMS, reinterpret_cast<unsigned char *>(g.window_sums.p), (const uint32_t *)nullptr);
     tm_mark("window_sum");
     RT_CHECK(rt_last());
-    if (g.windows_dst) RT_CHECK(rt_d2d(g.windows_dst, g.window_sums.p, (size_t)TABLE_SUMS * 128, st));
+    if (d_sums_dst) RT_CHECK(rt_d2d(d_sums_dst, g.window_sums.p, (size_t)TABLE_SUMS * 128, st));
     else RT_CHECK(rt_d2h(host_sums, g.window_sums.p, (size_t)TABLE_SUMS * 128, st));
     RT_CHECK(rt_sync(st));
     tm_end();

@@ -1,5 +1,6 @@
 // The MSM planner (msm_plan.hip): window width, GLV split or not, which shared-bucket set, and the width / set trials.  Host
-// code only: it reads the tuning knobs and the key's records, allocates nothing on the device and launches nothing.
+// code only: it reads the tuning knobs and the key's records, allocates nothing on the device and launches nothing.  What a
+// commit, a partial or a batch does with these answers -- its route -- is decided one level up, in msm_route.h.
 #pragma once
 #include "ctx.h"
 
@@ -25,7 +26,7 @@ const Bases::SharedSet *pick_shared(const Bases &bs, size_t n, uint32_t count, b
 // the key has the endomorphism copy of the GLV split, or the library may build one for it
 bool glv_possible(const Bases &bs);
 // the split is to be preferred to the plain path for this commit (pairs: the pairs of the submission); the caller still has to
-// have the copy (capi.hip: glv_ready)
+// have the copy (msm_route.h: GlvCopyFn; capi.hip: glv_ready)
 bool choose_glv(const Bases &bs, const MsmPlan &plain, const MsmPlan &split, size_t pairs);
 
 // Width trials (ctx.h: Bases::WidthTrial).  kind: bit 0 = GLV split, bit 1 = host scalars, bit 2 = a trial among the key's

@@ -219,7 +219,7 @@ MsmPlan make_plan(size_t n, int32_t forced_c, uint32_t count, uint64_t stride, c
     plan_reduction(p, 1);                                    // callers that can take several pieces per window ask again
     return p;
 }
-// Batches (capi.hip: msm_batch_device_locked).  The number of commitments per launch comes from the plan of ONE commitment; the
+// Batches (msm_route.hip: route_batch, route_batch_launch).  The number of commitments per launch comes from the plan of ONE commitment; the
 // plan of a launch of cnt commitments is then made for cnt of them, and it may pick another width -- the model of a batch is the
 // commit of n cnt pairs, whose rows favour wider windows.  So that its counters still fit one scan, that plan's widths are capped at
 // the widest c with ceil(bits / c) cnt 2^(c-1) <= SCAN_MAX_COUNTERS (without the cap, a key that opted into wide windows planned

@@ -1,4 +1,4 @@
-// The launches of a batch (msm_plan.hip: batch_per_launch, make_batch_plan, as capi.hip's msm_batch_device_locked forms them) for keys
+// The launches of a batch (msm_plan.hip: batch_per_launch, make_batch_plan, as msm_route.hip's route_batch forms them) for keys
 // that opted into wide windows and keys that did not: one line per (pairs, commitments, cmax, path) with the widest launch's
 // width and bucket counters.  tests/test_wide_windows_host.py checks that no launch holds more counters than one scan takes.
 #include <cstdio>
