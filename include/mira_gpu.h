@@ -163,6 +163,66 @@ int mira_msm_last_plan(int32_t *window_bits, int32_t *num_windows);
 /* ... and the width of the table set that commit went through (8 .. 16 shared buckets, 20 or 22 wide tables), 0 = none. */
 int mira_msm_last_table_bits(int32_t *table_bits);
 
+/* ---- a key's tuning, from one process to the next ----------------------------------------
+ * A key tunes itself while it works: the first ~10 commits of every shape (pairs, commitments per submission, path) run at the
+ * planner's width and its four neighbours, each twice (MIRA_TUNE_WIDTH_TRIALS), the first commits over several shared-bucket sets
+ * go through every set twice, and the planner works from the bit lengths of the PREVIOUS commit of a length.  None of it outlives
+ * the process; the reference's drivers fold one or two steps (examples/groth16/main.rs:285-298, benches/trivial/main.rs:111-148).
+ * mira_msm_tuning_export writes what the key has settled as a blob of bytes, mira_msm_tuning_import installs such a blob in a
+ * key registered later (right after mira_msm_register_bases* -- and after mira_msm_set_handle_max_window_bits and the table
+ * builds of mira_msm_precompute*, if the key gets any: they are part of the identity below; the caller keeps the bytes where it keeps the key's
+ * .cache/{label}/{k}.bin, src/commitment.rs:134-166).  A blob NEVER changes a result, only which width or set a commit runs at, and it
+ * records what was measured under the MIRA_TUNE_* knobs in force when the trials ran.  An imported record of the GLV split does
+ * not build the endomorphism copy early: mira_msm_precompute_ex(handle, MIRA_TABLE_GLV) does.  Neither call launches anything or
+ * touches device memory.
+ *
+ * export: *len_out is always the blob's full length; cap = 0 asks for it (buf may be NULL).  0 < cap < length -> MIRA_E_BAD_ARG,
+ * nothing written.  The same state gives the same bytes: no timestamps, no pointers.
+ *
+ * import, three outcomes:
+ *   malformed bytes            -> MIRA_E_BAD_ARG, the reason in mira_last_error(), *accepted_out = 0, the key unchanged
+ *   well-formed, other identity -> MIRA_OK, *accepted_out = 0, the key unchanged (a stale file costs nothing and is no error)
+ *   accepted                   -> MIRA_OK, *accepted_out = 1: every record is the finished trial of its shape (replacing the key's own
+ *                                 record of that shape, a running one included; the key still keeps 12 shapes, least recently
+ *                                 used out first), and the statistics slot, when present, is the key's
+ * The whole blob is validated before the key is touched.
+ *
+ * Layout, little-endian, no padding:
+ *   offset  size
+ *   0       8       magic "MIRATUNE"
+ *   8       4       u32 format version, 1
+ *   -- identity
+ *   12      4       u32 A, length of the architecture string, 1 .. 64
+ *   16      A       the device's architecture name up to the first ':' ("gfx950"; "emu" in the test-only emulation), no NUL
+ *   +0      8       u64 fingerprint of the planner's model: FNV-1a 64 over the bytes of its measured tables and trial schedule
+ *                   (a re-measured table retires every older blob by itself)
+ *   +8      4       u32 curve (MIRA_CURVE_*)
+ *   +12     8       u64 key length in points
+ *   +20     4       u32 max_c (mira_msm_set_handle_max_window_bits)
+ *   +24     4       u32 S, the number of shared-bucket sets, <= 32
+ *   +28     4 S     u32 their widths, in the order they were built
+ *   +0      4       u32 width of the wide tables (20 / 22), 0 = none
+ *   -- records: the FINISHED trials, sorted by (n, count, kind)
+ *   +4      4       u32 R <= 12
+ *   +8      32 R    per record: u64 n (pairs), u32 count (commitments per launch), u32 kind (bit 0 = GLV split, bit 1 = host
+ *                   scalars, bit 2 = a trial among the key's sets), u32 c0 (the model's width), u32 best_c (the width kept),
+ *                   f64 best_us (its measured wall time, IEEE 754 binary64)
+ *   -- statistics slot
+ *   +0      4       u32 1 = present (the key has statistics), 0 = absent
+ *   +4      8       u64 stat_n, the length of the commit they came from      } only when present
+ *   +12     4       u32 stat_kind: 0 = whole scalars, 1 = halves of the split }
+ *   +16     1024    256 x u32 counters, [b] = sampled values of bit length b  }
+ *   -- end
+ *   +0      8       u64 FNV-1a 64 (offset basis cbf29ce484222325, prime 100000001b3) over every byte before it
+ * Malformed: bad magic, version, length or checksum; trailing bytes; R > 12; two records of one shape; n = 0, n > key length,
+ * count = 0, kind > 7; a best_c no trial of that kind can have produced (plain: 4 .. max_c; GLV split: 5 .. 16; set trial: one of
+ * the S widths); a best_us that is negative or no number; a statistics flag other than 0 / 1, stat_n = 0 or > key length,
+ * stat_kind > 1, or counters that sum to more than twice the values histogrammed, 2 (stat_kind + 1) stat_n (the counters are a
+ * weighted sample of the scalars, so they add up to about, not exactly, stat_n values -- or 2 stat_n halves).  A blob is judged
+ * against the identity it states itself. */
+int mira_msm_tuning_export(uint64_t handle, void *buf, size_t cap, size_t *len_out);
+int mira_msm_tuning_import(uint64_t handle, const void *buf, size_t len, int32_t *accepted_out);
+
 /* Thresholds of the engine's internal choices, for tests and tuning runs (they never change a
  * result): the smallest MSM that takes the LDS-staged two-level sort, the smallest MSM that uses a
  * handle's window tables, the smallest commit whose scalar-length statistics plan the next one, and

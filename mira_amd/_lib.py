@@ -31,7 +31,7 @@ SYMBOLS = [
     "mira_msm_register_bases_file", "mira_msm_save_bases_file", "mira_msm_partial_to_device", "mira_msm_set_handle_window_bits",
     "mira_trim", "mira_dev_mem_info", "mira_msm_plan_window_bits", "mira_lincomb_multi_device", "mira_dev_copy", "mira_msm_last_table_bits",
     "mira_graph_specialize", "mira_graph_is_specialized", "mira_graph_jit_source", "mira_graph_jit_compile_check",
-    "mira_msm_set_handle_max_window_bits",
+    "mira_msm_set_handle_max_window_bits", "mira_msm_tuning_export", "mira_msm_tuning_import",
     "mira_batch_invert_device", "mira_lookup_m_device", "mira_lookup_h_g_device",
     "mira_count_ne_device", "mira_sum_sub_device", "mira_graph_check_compiled", "mira_perm_compile", "mira_perm_check_device", "mira_perm_free",
 ]
@@ -125,6 +125,7 @@ class MiraLib:
             "mira_set_tuning": [ctypes.c_int, ctypes.c_int64],
             "mira_msm_register_bases_file": [ctypes.c_int, ctypes.c_char_p, u32, ctypes.c_int, vp], "mira_msm_save_bases_file": [u64, ctypes.c_char_p],
             "mira_msm_partial_to_device": [u64, sz, vp, sz, vp, vp, vp], "mira_msm_set_handle_window_bits": [u64, i32], "mira_msm_set_handle_max_window_bits": [u64, i32],
+            "mira_msm_tuning_export": [u64, vp, sz, vp], "mira_msm_tuning_import": [u64, vp, sz, vp],
             "mira_trim": [sz, vp], "mira_dev_mem_info": [vp, vp], "mira_msm_plan_window_bits": [sz, vp],
             "mira_lincomb_multi_device": [ctypes.c_int, vp, sz, vp, sz, u64p, sz], "mira_dev_copy": [vp, vp, sz],
             "mira_batch_invert_device": [ctypes.c_int, vp, vp, sz], "mira_lookup_m_device": [ctypes.c_int, vp, vp, sz, vp, sz],

@@ -210,6 +210,55 @@ class CommitmentKey:
         mira_msm_set_handle_max_window_bits.  Wide windows cut the additions of large commits for more bucket workspace."""
         self.lib.check(self.lib.c.mira_msm_set_handle_max_window_bits(self.handle, cmax))
 
+    # ---- the key's MSM tuning, from one process to the next (mira_msm_tuning_export / _import) ----
+    def export_tuning(self):
+        """What this key has settled about its own commits -- the finished width and set trials of its shapes, the bit-length
+        statistics of its last commit -- as bytes (layout: include/mira_gpu.h).  The same state gives the same bytes."""
+        n = ctypes.c_size_t()
+        self.lib.check(self.lib.c.mira_msm_tuning_export(self.handle, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(n.value)
+        self.lib.check(self.lib.c.mira_msm_tuning_export(self.handle, buf, n.value, ctypes.byref(n)))
+        return buf.raw[:n.value]
+
+    def import_tuning(self, blob):
+        """Install a blob of export_tuning, best right after the key is registered: its shapes then commit at the settled widths
+        from the first commit on.  True: accepted; False: a well-formed blob of another device, planner model or key (nothing
+        changed, no error).  Malformed bytes raise MiraError (MIRA_E_BAD_ARG) and change nothing.  Never changes a result.
+        A record of the GLV split does not build the endomorphism copy early: precompute(_lib.TABLE_GLV) does."""
+        blob = bytes(blob)
+        ok = ctypes.c_int32()
+        self.lib.check(self.lib.c.mira_msm_tuning_import(self.handle, blob, len(blob), ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def save_tuning(self, path):
+        """export_tuning into `path` -- beside the key's `{cache_folder}/{label}/{k}.bin`, say -- through a temporary file in the
+        same directory and a rename: a reader never sees half a blob."""
+        import os
+        import tempfile
+        path = os.fspath(path)
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(path) or ".")
+        try:
+            with os.fdopen(fd, "wb") as f:
+                f.write(self.export_tuning())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+
+    def load_tuning(self, path):
+        """import_tuning of the file at `path`; False when there is none."""
+        try:
+            with open(path, "rb") as f:
+                blob = f.read()
+        except FileNotFoundError:
+            return False
+        return self.import_tuning(blob)
+
+    def tuning_records(self, blob=None):
+        """What a key has learned, readable: parse_tuning of `blob`, or of this key's own export."""
+        return parse_tuning(self.export_tuning() if blob is None else blob)
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.c.mira_msm_unregister(self.handle)
@@ -220,6 +269,58 @@ class CommitmentKey:
             self.close()
         except Exception:
             pass
+
+
+class TuningRecords(list):
+    """The records of a tuning blob, one dict (n, count, kind, c0, best_c, best_us) each, in the blob's order; `stats` is its
+    statistics slot -- dict (n, kind, hist) or None -- and `identity` what the blob says it was tuned on."""
+    stats = None
+    identity = None
+
+
+def fnv1a64(data):
+    h = 0xcbf29ce484222325
+    for b in data:
+        h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def parse_tuning(blob):
+    """A blob of CommitmentKey.export_tuning by the layout of include/mira_gpu.h (mira_msm_tuning_export).  Reads the structure
+    only -- magic, version, checksum, lengths; ValueError otherwise -- and leaves judging the values to the library's import."""
+    import struct
+    blob = bytes(blob)
+    if len(blob) < 20 or blob[:8] != b"MIRATUNE":
+        raise ValueError("not a tuning blob")
+    if struct.unpack_from("<Q", blob, len(blob) - 8)[0] != fnv1a64(blob[:-8]):
+        raise ValueError("tuning blob: checksum mismatch")
+    at = 8
+
+    def take(fmt):
+        nonlocal at
+        if at + struct.calcsize(fmt) > len(blob) - 8:
+            raise ValueError("tuning blob: truncated")
+        v = struct.unpack_from(fmt, blob, at)
+        at += struct.calcsize(fmt)
+        return v
+    version, arch_len = take("<II")
+    if version != 1:
+        raise ValueError("tuning blob: unknown format version %d" % version)
+    arch, = take("<%ds" % arch_len)
+    model, curve, n, max_c, nsets = take("<QIQII")
+    sets = list(take("<%dI" % nsets))
+    table_c, nrec = take("<II")
+    out = TuningRecords()
+    out.identity = dict(arch=arch.decode("latin-1"), model=model, curve=curve, n=n, max_c=max_c, sets=sets, table_c=table_c)
+    for _ in range(nrec):
+        out.append(dict(zip(("n", "count", "kind", "c0", "best_c", "best_us"), take("<QIIIId"))))
+    has_stats, = take("<I")
+    if has_stats:
+        stat_n, stat_kind = take("<QI")
+        out.stats = dict(n=stat_n, kind=stat_kind, hist=list(take("<256I")))
+    if at != len(blob) - 8:
+        raise ValueError("tuning blob: trailing bytes")
+    return out
 
 
 def combine_partials(curve, partials, window_bits, num_windows, lib=None):

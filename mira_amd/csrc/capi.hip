@@ -6,6 +6,7 @@
 #include "glv_consts.h"
 #include "host_curve.hpp"
 #include "msm_route.h"
+#include "msm_tuning.h"
 #include <cerrno>
 #include <chrono>
 #include <fcntl.h>
@@ -525,6 +526,55 @@ int mira_msm_set_handle_max_window_bits(uint64_t handle, int32_t cmax) {
     if (bs->max_c != (uint32_t)cmax) { bs->max_c = (uint32_t)cmax; bs->trials.clear(); }   // the width trials start again
     return MIRA_OK;
 }
+// ---- a key's tuning as bytes (msm_tuning.hip): nothing is launched, no device memory is touched
+// the architecture a blob was tuned on: the device's gcn arch name up to the first ':' (gfx950:sramecc+:xnack- -> gfx950)
+static int tuning_arch(std::string *arch) {
+#ifndef MIRA_CPU_EMU
+    static std::string name;                                 // (under the library lock; the bound device does not change once a key exists)
+    if (name.empty()) {
+        hipDeviceProp_t prop;
+        RT_CHECK(hipGetDeviceProperties(&prop, g.device));
+        name = prop.gcnArchName;
+        name = name.substr(0, name.find(':'));
+        if (name.empty()) name = "unknown";
+    }
+    *arch = name;
+#else
+    *arch = "emu";
+#endif
+    return MIRA_OK;
+}
+int mira_msm_tuning_export(uint64_t handle, void *buf, size_t cap, size_t *len_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (!len_out || (cap && !buf)) { set_error("null output"); return MIRA_E_BAD_ARG; }
+    const Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    std::string arch;
+    int rc = tuning_arch(&arch);
+    if (rc) return rc;
+    std::vector<unsigned char> bytes;
+    tuning_export(*bs, arch.c_str(), &bytes);
+    *len_out = bytes.size();
+    if (cap == 0) return MIRA_OK;                            // the size query
+    if (cap < bytes.size()) { set_error("tuning buffer too small: " + std::to_string(cap) + " bytes, the blob has " + std::to_string(bytes.size())); return MIRA_E_BAD_ARG; }
+    memcpy(buf, bytes.data(), bytes.size());
+    return MIRA_OK;
+}
+int mira_msm_tuning_import(uint64_t handle, const void *buf, size_t len, int32_t *accepted_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (!accepted_out) { set_error("null output"); return MIRA_E_BAD_ARG; }
+    *accepted_out = 0;
+    if (!buf) { set_error("null tuning blob"); return MIRA_E_BAD_ARG; }
+    const Bases *bs = find_bases(handle);
+    if (!bs) return MIRA_E_BAD_ARG;
+    std::string arch, err;
+    int rc = tuning_arch(&arch);
+    if (rc) return rc;
+    rc = tuning_import(*bs, arch.c_str(), buf, len, accepted_out, &err);
+    if (rc) set_error(err);
+    return rc;
+}
+
 int mira_msm_partial_to_device(uint64_t handle, size_t first, const void *d_scalars, size_t n, void *d_out_partial,
                                int32_t *window_bits, int32_t *num_windows) {
     std::lock_guard<std::mutex> lk(g_lock);

@@ -37,3 +37,14 @@ static inline uint32_t trial_width(const Bases::WidthTrial &t) { return t.done ?
 const Bases::SharedSet *trial_set(const Bases &bs, const Bases::WidthTrial &t, const Bases::SharedSet *model);
 // the wall time of the commit that ran under trial_width(t)
 void trial_report(Bases::WidthTrial &t, double us, const Bases &bs);
+
+// What a record that outlives the process may hold (msm_tuning.h): a width trial_candidate's rules could have produced for this
+// kind -- plain 4 .. max_c, the halves of the GLV split 5 .. 16, a set trial one of set_widths -- and the fingerprint of the model
+// the trials checked: FNV-1a 64 over the bytes of the measured tables, TRIAL_RUNS and TRIAL_OFFSETS.
+static inline uint64_t fnv1a64(const void *data, size_t len, uint64_t h = 0xcbf29ce484222325ull) {   // (h: the hash so far, to go on from)
+    const unsigned char *p = static_cast<const unsigned char *>(data);
+    for (size_t i = 0; i < len; i++) { h ^= p[i]; h *= 0x100000001b3ull; }
+    return h;
+}
+bool trial_width_possible(uint32_t kind, uint32_t c, uint32_t max_c, const uint32_t *set_widths, size_t nsets);
+uint64_t plan_model_fingerprint();

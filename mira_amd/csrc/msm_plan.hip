@@ -355,4 +355,24 @@ void trial_report(Bases::WidthTrial &t, double us, const Bases &bs) {
         if (const uint32_t c = trial_candidate(t, bs, (size_t)t.steps++)) { t.cur_c = c; t.cur_runs = 0; return; }
     t.done = true;
 }
-
+// ---- what a persisted record may hold (msm_tuning.hip) ---------------------------------------------------------------------------
+// a width trial_candidate's rules (or the model, which plans within the same ranges) could have left in a record of this kind,
+// over a key with this max_c and these shared-bucket sets
+bool trial_width_possible(uint32_t kind, uint32_t c, uint32_t max_c, const uint32_t *set_widths, size_t nsets) {
+    if (kind & 4) {
+        for (size_t k = 0; k < nsets; k++) if (set_widths[k] == c) return true;
+        return false;
+    }
+    return c >= ((kind & 1) ? 5u : 4u) && c <= ((kind & 1) ? MSM_MAX_NARROW_C : max_c);
+}
+// FNV-1a 64 over the bytes of the measured tables and the trial schedule themselves: a re-measured table or another schedule is
+// another model, and what was tuned under the old one is not carried over (msm_tuning.hip keeps it in a blob's identity)
+uint64_t plan_model_fingerprint() {
+    uint64_t h = fnv1a64(nullptr, 0);
+    auto add = [&h](const void *data, size_t len) { h = fnv1a64(data, len, h); };
+    for (const MeasuredWalls *w : {&PLAN_WALLS, &GLV_WALLS, &SHARED_WALLS, &WIDE_WALLS}) {
+        add(&w->rows, sizeof w->rows); add(w->log_n, sizeof w->log_n); add(w->wall_us, sizeof w->wall_us);
+    }
+    add(&TRIAL_RUNS, sizeof TRIAL_RUNS); add(TRIAL_OFFSETS, sizeof TRIAL_OFFSETS);
+    return h;
+}
