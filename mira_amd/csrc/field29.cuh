@@ -4,9 +4,9 @@
 // saturated 8 x 32-bit CIOS multiplier spends two thirds of its issue slots on zero-extending
 // moves and 64-bit carry adds around its 128 multiply-adds (measured: 1805 cycles per wave
 // multiplication).  With 29-bit limbs a 64-bit column holds nine 58-60-bit products plus the nine
-// Montgomery reduction products without overflow, so every partial product is one in-place
+// Montgomery reduction products without overflow, so every partial product is one
 // `acc += a_i * b_j` (v_mad_u64_u32 with the accumulator as its own addend), and carries are
-// resolved once per column.
+// resolved once per column -- as the addend that seeds the next column's chain (f29_column_serial).
 //
 // Representation ("loose"): value = sum l[i] * 2^(29 i), every limb < 2^29 + 2^5, value < 11 P,
 // congruent to x * 2^261 mod P (Montgomery form with R' = 2^261).  Multiplication accepts limbs
@@ -226,11 +226,85 @@ template <class F> inline void f29_check_columns2(const Fe29<F> &a, const Fe29<F
 #define F29_CHECK_COLUMNS2(a, b, c, d) ((void)0)
 #endif
 
+// host test builds may watch every column as it completes (tests/emu/test_f29_column_serial.cpp).  Never define it for device
+// code: any further use of the sum changes what the compiler makes of the chain below.
+#ifndef F29_COLUMN_HOOK
+#define F29_COLUMN_HOOK(k, v) ((void)0)
+#endif
+// F29_COLUMN_SERIAL (default 1): the multipliers sum one column at a time, as one chain of multiply-adds seeded with the
+// carry of the column before (product scanning), so the carry rides in v_mad_u64_u32's 64-bit addend and there is no
+// separate 64-bit `c[k + 1] += c[k] >> 29` -- 17 v_lshl_add_u64 less per reduction.  Every column holds the same integer as
+// in the in-place form (F29_COLUMN_SERIAL=0, kept for A/B builds: `make EXTRA=-DF29_COLUMN_SERIAL=0`), so results are
+// bit for bit the same and the column bounds above hold unchanged.
+#ifndef F29_COLUMN_SERIAL
+#define F29_COLUMN_SERIAL 1
+#endif
+#if F29_COLUMN_SERIAL
+// t + a * b.  On the device every sum gets a second, empty use: LLVM otherwise re-associates a column's chain (products
+// first, carry last) and the 64-bit carry add is back.  The use is an input-only asm, which defines no register: the hazard
+// recogniser assumes that any asm *result* may be forwarded like a dst_sel write and pads an instruction that reads it
+// right away with an s_nop -- `asm("" : "+v"(t))` costs one beside nearly every multiply-add, although dependent
+// v_mad_u64_u32 themselves need no wait state.  An asm without a result has to be volatile to stay, and LLVM takes a
+// volatile asm for a memory access: an operand read through a reference into LDS or global memory would be loaded again for
+// every product, so the multipliers copy their operands into F29Limbs first (free when they are in registers already).
+// Host builds: the same order in plain C++.
+HD uint64_t f29_mad(uint32_t a, uint32_t b, uint64_t t) {
+    t += (uint64_t)a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : : "v"(t));
+#endif
+    return t;
+}
+struct F29Limbs {
+    uint32_t l[9];
+    template <class F> HD explicit F29Limbs(const Fe29<F> &a) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) l[i] = a.l[i];
+    }
+};
+// The reduction around a column sum: `col(k, t)` returns t plus the operand terms of column k (0 <= k < 17).
+template <class F, class Col> HD Fe29<F> f29_column_serial(Col col) {
+    uint32_t m[9];
+    uint64_t t = 0;
+    Fe29<F> r;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        t = col(k, t);
+#pragma unroll
+        for (int j = 0; j < k; j++) t = f29_mad(m[j], F::P[k - j], t);
+        m[k] = ((uint32_t)t * F::N0) & M29;
+        t = f29_mad(m[k], F::P[0], t);
+        F29_COLUMN_HOOK(k, t);
+        t >>= 29;
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+        t = col(k, t);
+#pragma unroll
+        for (int j = k - 8; j < 9; j++) t = f29_mad(m[j], F::P[k - j], t);
+        F29_COLUMN_HOOK(k, t);
+        r.l[k - 9] = (uint32_t)t & M29;
+        t >>= 29;
+    }
+    F29_COLUMN_HOOK(17, t);
+    r.l[8] = (uint32_t)t;
+    return r;
+}
+#endif
+
 // Montgomery product a * b * 2^-261 mod P.  Limbs of a and b < 2^30 (or one of them carried and the
 // other < 2^31.5, see above); result loose, < 1.5 P for a * b < 64 P^2.
 template <class F> HD Fe29<F> f29_mul(const Fe29<F> &a, const Fe29<F> &b) {
     F29_ASSERT(F29_GET(a) * F29_GET(b) <= F29_RP_OVER_P);
     F29_CHECK_COLUMNS(a, b);
+#if F29_COLUMN_SERIAL
+    const F29Limbs x(a), y(b);
+    Fe29<F> r = f29_column_serial<F>([&](int k, uint64_t t) {
+#pragma unroll
+        for (int i = (k < 9 ? 0 : k - 8); i <= (k < 9 ? k : 8); i++) t = f29_mad(x.l[i], y.l[k - i], t);
+        return t;
+    });
+#else
     uint64_t c[18];
 #pragma unroll
     for (int k = 0; k < 18; k++) c[k] = 0;
@@ -252,6 +326,7 @@ template <class F> HD Fe29<F> f29_mul(const Fe29<F> &a, const Fe29<F> &b) {
         c[i + 1] += c[i] >> 29;
     }
     r.l[8] = (uint32_t)c[17];
+#endif
     F29_SET(r, F29_GET(a) * F29_GET(b) / 168.9 + 1.0);
     return r;
 }
@@ -263,6 +338,16 @@ template <class F> HD Fe29<F> f29_mul(const Fe29<F> &a, const Fe29<F> &b) {
 template <class F> HD Fe29<F> f29_mul2_add(const Fe29<F> &a, const Fe29<F> &b, const Fe29<F> &c2, const Fe29<F> &d) {
     F29_ASSERT(F29_GET(a) * F29_GET(b) + F29_GET(c2) * F29_GET(d) <= F29_RP_OVER_P);
     F29_CHECK_COLUMNS2(a, b, c2, d);
+#if F29_COLUMN_SERIAL
+    const F29Limbs x(a), y(b), z(c2), w(d);
+    Fe29<F> r = f29_column_serial<F>([&](int k, uint64_t t) {
+#pragma unroll
+        for (int i = (k < 9 ? 0 : k - 8); i <= (k < 9 ? k : 8); i++) t = f29_mad(x.l[i], y.l[k - i], t);
+#pragma unroll
+        for (int i = (k < 9 ? 0 : k - 8); i <= (k < 9 ? k : 8); i++) t = f29_mad(z.l[i], w.l[k - i], t);
+        return t;
+    });
+#else
     uint64_t c[18];
 #pragma unroll
     for (int k = 0; k < 18; k++) c[k] = 0;
@@ -288,6 +373,7 @@ template <class F> HD Fe29<F> f29_mul2_add(const Fe29<F> &a, const Fe29<F> &b, c
         c[i + 1] += c[i] >> 29;
     }
     r.l[8] = (uint32_t)c[17];
+#endif
     F29_SET(r, (F29_GET(a) * F29_GET(b) + F29_GET(c2) * F29_GET(d)) / 168.9 + 1.0);
     return r;
 }
@@ -296,6 +382,10 @@ template <class F> HD Fe29<F> f29_mul2_add(const Fe29<F> &a, const Fe29<F> &b, c
 // The NTT's last pass ends with it: the pass before has multiplied every element by 2^261 (and the ifft scale) inside
 // its post-twiddle, so the value that leaves is exact and < 2 P.
 template <class F> HD Fe29<F> f29_redc(const Fe29<F> &a) {
+#if F29_COLUMN_SERIAL
+    const F29Limbs x(a);
+    Fe29<F> r = f29_column_serial<F>([&](int k, uint64_t t) { return k < 9 ? t + x.l[k] : t; });
+#else
     uint64_t c[18];
 #pragma unroll
     for (int k = 0; k < 9; k++) { c[k] = a.l[k]; c[k + 9] = 0; }
@@ -313,11 +403,24 @@ template <class F> HD Fe29<F> f29_redc(const Fe29<F> &a) {
         c[i + 1] += c[i] >> 29;
     }
     r.l[8] = (uint32_t)c[17];
+#endif
     F29_SET(r, F29_GET(a) / 168.9 + 1.0);
     return r;
 }
 template <class F> HD Fe29<F> f29_sqr(const Fe29<F> &a) {
     F29_ASSERT(F29_GET(a) * F29_GET(a) <= F29_RP_OVER_P);
+#if F29_COLUMN_SERIAL
+    const F29Limbs x(a);
+    uint32_t d[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) d[i] = x.l[i] << 1;
+    Fe29<F> r = f29_column_serial<F>([&](int k, uint64_t t) {          // 45 products: a_i * 2 a_j for i < j, a_i^2 on the even columns
+#pragma unroll
+        for (int i = (k < 9 ? 0 : k - 8); 2 * i < k; i++) t = f29_mad(x.l[i], d[k - i], t);
+        if (k % 2 == 0) t = f29_mad(x.l[k / 2], x.l[k / 2], t);
+        return t;
+    });
+#else
     uint64_t c[18];
 #pragma unroll
     for (int k = 0; k < 18; k++) c[k] = 0;
@@ -344,6 +447,7 @@ template <class F> HD Fe29<F> f29_sqr(const Fe29<F> &a) {
         c[i + 1] += c[i] >> 29;
     }
     r.l[8] = (uint32_t)c[17];
+#endif
     F29_SET(r, F29_GET(a) * F29_GET(a) / 168.9 + 1.0);
     return r;
 }

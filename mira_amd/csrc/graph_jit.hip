@@ -30,7 +30,11 @@ Rtc &rtc() {
     }();
     return loaded;
 }
-static const char *const JIT_OPTIONS[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
+// A specialised kernel keeps the in-place multiplier (field29.cuh: F29_COLUMN_SERIAL): hiprtc compiles its straight-line program of
+// several hundred products four times slower around the column-serial form (10.8 -> 46 s for the main gate's kernels, LAB_NOTES),
+// for 3 % of evaluation throughput.  Compiled once per circuit, but in front of its first fold.
+static const char *const JIT_OPTIONS[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-DF29_COLUMN_SERIAL=0"};
+static constexpr int JIT_OPTION_COUNT = (int)(sizeof(JIT_OPTIONS) / sizeof(JIT_OPTIONS[0]));
 std::vector<char> compile(const std::string &src, std::string &err) {
     Rtc &r = rtc();
     std::vector<char> out;
@@ -41,7 +45,7 @@ std::vector<char> compile(const std::string &src, std::string &err) {
         err = "hiprtcCreateProgram failed";
         return out;
     }
-    const int rc = r.compile(prog, 3, const_cast<const char **>(JIT_OPTIONS));
+    const int rc = r.compile(prog, JIT_OPTION_COUNT, const_cast<const char **>(JIT_OPTIONS));
     if (rc != 0) {
         size_t n = 0;
         (void)r.log_size(prog, &n);

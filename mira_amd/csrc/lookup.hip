@@ -1,4 +1,14 @@
 // Host side of the lookup-argument kernels (lookup_kernels.cuh): batch inversion, the multiplicities m and the fused h, g.
+// The device code of this unit keeps the in-place multiplier (field29.cuh: F29_COLUMN_SERIAL): k_inv_top, whose Fermat chain
+// keeps an accumulator and an LDS table across loops, compiles worse around the column-serial form (128 VGPRs with 6 spilled
+// against 89, 4 158 VALU instructions against 2 992 for the same 1 321 multiply-adds), and the other kernels here are
+// latency-bound tails.  Device code only: a unit's device code is a code object of its own, while the host bodies of the inline
+// multipliers are shared by every unit of the library and must be the same everywhere.
+// (decide.hip includes lookup_kernels.cuh too and compiles what it uses of it column-serial; k_inv_top is launched from here only.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#undef F29_COLUMN_SERIAL
+#define F29_COLUMN_SERIAL 0
+#endif
 #include "ctx.h"
 #include "lookup_kernels.cuh"
 
