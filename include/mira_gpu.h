@@ -290,6 +290,10 @@ int mira_msm_tuning_import(uint64_t handle, const void *buf, size_t len, int32_t
  * most 2048).  Tests use it to reach several workgroups at small sizes.
  * Never changes a result */
 #define MIRA_TUNE_DECIDE_GRID 23
+/* points per chunk of mira_setup_bases_device / mira_msm_setup_bases: the host squeezes 32 bytes of SHAKE256 per point into one of
+ * two pinned buffers while the kernels of the chunk before run; 16 .. 2^24, default 2^18 (anything else that is not negative ->
+ * MIRA_E_BAD_ARG).  Tests set it small so that chunk boundaries fall inside the sponge's 136-byte blocks.  Never changes a result */
+#define MIRA_TUNE_SETUP_CHUNK 24
 int mira_set_tuning(int knob, int64_t value);
 
 /* Read a range of the registered key back in the reference layout (cache file writing,
@@ -536,6 +540,31 @@ int mira_get_omega_or_inv(uint32_t k, int is_inverse, uint64_t out[4]);
  * index0 = global index of the first element (lets ranks generate their own chunk).          */
 int mira_synth_scalars_device(int curve, size_t n, uint64_t index0, uint64_t seed, int kind, void *d_out);
 int mira_synth_bases_device(int curve, size_t n, uint64_t index0, uint64_t seed, void *d_out);
+
+/* ---- CommitmentKey::setup(k, label), src/commitment.rs:52-76: a transparent key by hash-to-curve ------------------------
+ * Point i of the key of `label` comes from bytes [32 i, 32 i + 32) of SHAKE256(label) (src/commitment.rs:58-65):
+ *   hash_to_field  expand_message_xmd over BLAKE2b-512, DST = "from_uniform_bytes-" curve_id "_XMD:BLAKE2b_SVDW_RO_" byte(length),
+ *                  curve_id = "bn256_g1" / "grumpkin_g1": two field elements u_0, u_1 (512 bits each, reduced mod p)
+ *   map            Shallue-van de Woestijne (RFC 9380 appendix F.1, Z = 1) of each, and P_i = map(u_0) + map(u_1) by the full group law
+ * Nobody knows a discrete logarithm between two such points -- unlike the bases of mira_synth_bases_device, which are public
+ * multiples of the generator and serve benchmarks only.  The curve hashing the reference calls lives in halo2curves, which is not
+ * part of it: these keys equal the project's own restatement (tests/setup_ref.py) and its recorded checksums and are UNPINNED
+ * AGAINST halo2curves.  The reference's load_from_file / load_or_setup_cache read what mira_msm_save_bases_file writes of them.
+ * Points leave in the reference layout (x * 2^256, y * 2^256, 4 x u64 each; the identity as 64 zero bytes); device pointers are
+ * 16-byte aligned.  The stream is squeezed on the host in chunks of MIRA_TUNE_SETUP_CHUNK points beside the kernels; with timing
+ * on, mira_get_timings reports setup_squeeze_host (host time), setup_hash and setup_map (device, summed over the first 63 chunks; a
+ * chunk's setup_hash interval includes its wait for the chunk's bytes -- the two stages on their own report the kernel alone). */
+/* setup, src/commitment.rs:52-76: points [first, first + n) of the key of `label` (any n; the same bytes as that slice of a longer
+ * key: a shard generates its own range).  first + n > 2^32 or a null pointer with a non-zero length -> MIRA_E_BAD_ARG */
+int mira_setup_bases_device(int curve, const void *label, size_t label_len, uint64_t first, size_t n, void *d_out /* n * 64 B */);
+/* setup, src/commitment.rs:52-76, then registered as a resident key of 2^k points (as mira_msm_register_bases_device of the
+ * above, without the intermediate copy).  k >= 32 -> MIRA_E_BAD_ARG (the reference asserts k < 32, src/commitment.rs:53) */
+int mira_msm_setup_bases(int curve, uint32_t k, const void *label, size_t label_len, uint64_t *handle_out);
+/* the two stages of setup, src/commitment.rs:52-76, on their own (neither hashing nor the stream reaches the map's exceptional
+ * inputs): n messages of 32 bytes -> n x 2 field elements (Montgomery form, canonical); n x 2 canonical field elements -> n points.
+ * d_points may be d_u */
+int mira_hash_to_field_device(int curve, const void *d_msgs /* n * 32 B */, size_t n, void *d_u /* n * 2 elements */);
+int mira_map_to_curve_device(int curve, const void *d_u /* n * 2 elements */, size_t n, void *d_points /* n * 64 B */);
 
 /* ---- library-held device memory ------------------------------------------------------------
  * Workspaces (digit, sort and bucket buffers; NTT temporaries and the four cached twiddle-table sets,

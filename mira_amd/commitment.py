@@ -48,9 +48,9 @@ class CommitmentKey:
 
     @classmethod
     def synthetic(cls, curve, n, seed=0x42415345, index0=0, lib=None):
-        """n deterministic bases P_i = k_i * G generated on the GPU; this is the
-        benchmark's stand-in for `setup` (src/commitment.rs:52-76), whose hash-to-curve lives in
-        the absent halo2curves crate."""
+        """n deterministic bases P_i = k_i * G generated on the GPU, the k_i derived from the public seed.
+        FOR BENCHMARKS AND TESTS ONLY: everyone who knows the seed knows every discrete logarithm between these bases and
+        can open a commitment under them to anything.  `setup` makes a key nobody knows a relation in."""
         lib = lib or _lib.load()
         ptr = lib.alloc(max(n, 1) * 64)
         try:
@@ -58,6 +58,25 @@ class CommitmentKey:
             return cls(curve, device_ptr=ptr, length=n, lib=lib)
         finally:
             lib.free(ptr)                               # register keeps its own resident copy: one copy of the key in HBM
+
+    @classmethod
+    def setup(cls, curve, k, label, lib=None):
+        """`CommitmentKey::setup(k, label)` (src/commitment.rs:52-76): 2^k bases by hash-to-curve, generated on the GPU
+        (mira_msm_setup_bases).  Point i comes from bytes [32 i, 32 i + 32) of SHAKE256(label) through hash_to_field
+        (expand_message_xmd over BLAKE2b-512) and the Shallue-van de Woestijne map; nobody knows a discrete logarithm
+        between two of them.  The derivation is written down in include/mira_gpu.h and restated in tests/setup_ref.py: the
+        keys equal that restatement and its recorded checksums and are unpinned against halo2curves, whose hashing the
+        reference calls.  k >= 32 raises ValueError, as the reference asserts."""
+        if not 0 <= k < 32:
+            raise ValueError(f"setup: k = {k} is not below 32")
+        label = label.encode() if isinstance(label, str) else bytes(label)
+        self = cls.__new__(cls)
+        self.lib = lib or _lib.load()
+        self.curve, self._len = curve, 1 << k
+        h = ctypes.c_uint64()
+        self.lib.check(self.lib.c.mira_msm_setup_bases(curve, k, label, len(label), ctypes.byref(h)))
+        self.handle = h.value
+        return self
 
     def __len__(self):
         return self._len
@@ -109,16 +128,21 @@ class CommitmentKey:
         return self
 
     @classmethod
-    def load_or_setup_cache(cls, curve, cache_folder, label, k, lib=None):
+    def load_or_setup_cache(cls, curve, cache_folder, label, k, lib=None, generator="synthetic"):
         """`load_or_setup_cache` (src/commitment.rs:134-166): `{cache_folder}/{label}/{k}.bin`;
         a loaded key is validated point by point (is_on_curve) on the GPU and rejected with the
-        reference's message otherwise.  A missing file is generated and stored -- with the
-        synthetic generator here, because `setup`'s hash-to-curve lives in the absent halo2curves."""
+        reference's message otherwise.  A missing file is generated and stored by `generator`:
+          "synthetic" (the default, as before)  `synthetic`: bases with KNOWN discrete logarithms, for benchmarks and tests
+                                                only -- the file lies where the reference's own load_or_setup_cache looks
+                                                and it would trust it: never use such a key to commit to anything real;
+          "hash"                                `setup(curve, k, label)`: a transparent key by hash-to-curve."""
         import os
+        if generator not in ("synthetic", "hash"):
+            raise ValueError(f"unknown generator {generator!r}")
         path = os.path.join(cache_folder, label, f"{k}.bin")
         if os.path.exists(path):
             return cls.load_from_file(curve, path, k, lib=lib, validate=True)
-        key = cls.synthetic(curve, 1 << k, lib=lib)
+        key = cls.setup(curve, k, label, lib=lib) if generator == "hash" else cls.synthetic(curve, 1 << k, lib=lib)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         key.save_to_file(path)
         return key

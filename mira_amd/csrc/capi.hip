@@ -480,8 +480,9 @@ int mira_msm_combine(int curve, const uint64_t *partials, size_t nparts, int32_t
 }
 int mira_set_tuning(int knob, int64_t value) {
     std::lock_guard<std::mutex> lk(g_lock);
-    if (knob < 0 || knob > MIRA_TUNE_DECIDE_GRID || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
+    if (knob < 0 || knob > MIRA_TUNE_SETUP_CHUNK || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
     if (knob == MIRA_TUNE_DECIDE_GRID && (value == 0 || value > 2048)) { set_error("MIRA_TUNE_DECIDE_GRID takes 1 .. 2048 workgroups (negative: the default)"); return MIRA_E_BAD_ARG; }
+    if (knob == MIRA_TUNE_SETUP_CHUNK && value >= 0 && (value < 16 || value > (1 << 24))) { set_error("MIRA_TUNE_SETUP_CHUNK takes 16 .. 2^24 points (negative: the default)"); return MIRA_E_BAD_ARG; }
     g.tune[knob] = value;
     return MIRA_OK;
 }
@@ -651,7 +652,7 @@ int mira_trim(size_t keep_bytes, size_t *released_out) {
     std::vector<DevBuf *> bufs = {&g.digits, &g.counts, &g.offsets, &g.cursor, &g.block_sums, &g.sorted_idx, &g.bucket_sums, &g.part, &g.coarse_offsets,
                                   &g.fine_counts, &g.fine_cursor, &g.head_part, &g.tail_part, &g.tail_key, &g.heavy, &g.heavy_out, &g.chunks, &g.window_sums,
                                   &g.scalars_stage, &g.ntt_tmp, &g.ntt_stage, &g.graph_ws, &g.tree_a, &g.tree_b, &g.hist_dev,
-                                  &g.inv_ws, &g.lk_owner, &g.lk_first, &g.lk_count, &g.lk_slot, &g.decide_parts, &g.decide_eval, &g.decide_inst};
+                                  &g.inv_ws, &g.lk_owner, &g.lk_first, &g.lk_count, &g.lk_slot, &g.decide_parts, &g.decide_eval, &g.decide_inst, &g.setup_stage};
     for (int i = 0; i < Ctx::NTT_SETS; i++) bufs.push_back(&g.ntt_set[i]);
     size_t total = 0;
     for (DevBuf *b : bufs) total += b->cap;
@@ -1012,6 +1013,49 @@ int mira_synth_bases_device(int curve, size_t n, uint64_t index0, uint64_t seed,
     if (!curve_ok(curve) || (n && !d_out)) { set_error("bad synth arguments"); return MIRA_E_BAD_ARG; }
     if (!n) return MIRA_OK;
     return curve_ops(curve).synth_bases(n, index0, seed, d_out);
+}
+
+// CommitmentKey::setup (src/commitment.rs:52-76): the derivation is stated in include/mira_gpu.h, its host side is setup.hip
+static bool setup_range_ok(const void *label, size_t label_len, uint64_t first, size_t n) {
+    return (label || !label_len) && first <= ((uint64_t)1 << 32) && n <= ((uint64_t)1 << 32) - first;
+}
+int mira_setup_bases_device(int curve, const void *label, size_t label_len, uint64_t first, size_t n, void *d_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (!curve_ok(curve) || !setup_range_ok(label, label_len, first, n) || (n && !d_out)) { set_error("bad setup arguments"); return MIRA_E_BAD_ARG; }
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!n) return MIRA_OK;
+    return setup_bases_device(curve, reinterpret_cast<const unsigned char *>(label), label_len, first, n, d_out, false);
+}
+int mira_msm_setup_bases(int curve, uint32_t k, const void *label, size_t label_len, uint64_t *handle_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (k >= 32) { set_error("setup: k = " + std::to_string(k) + " is not below 32"); return MIRA_E_BAD_ARG; }   // assert!(k < 32), src/commitment.rs:53
+    if (!curve_ok(curve) || !handle_out || (!label && label_len)) { set_error("bad setup arguments"); return MIRA_E_BAD_ARG; }
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    Bases b; b.curve = curve; b.n = (size_t)1 << k; b.owned = true;
+    if (rt_malloc(&b.d, b.n * 64) != hipSuccess || !b.d) { set_error("device allocation for bases failed"); return MIRA_E_ALLOC; }
+    // straight into the resident layout: no second sweep to convert the key
+    if ((rc = setup_bases_device(curve, reinterpret_cast<const unsigned char *>(label), label_len, 0, b.n, b.d, true))) { (void)rt_free(b.d); return rc; }
+    *handle_out = g.next_handle++;
+    g_bases[*handle_out] = b;
+    return MIRA_OK;
+}
+int mira_hash_to_field_device(int curve, const void *d_msgs, size_t n, void *d_u) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (!curve_ok(curve) || (n && (!d_msgs || !d_u)) || n > ((uint64_t)1 << 32)) { set_error("bad hash_to_field arguments"); return MIRA_E_BAD_ARG; }
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!n) return MIRA_OK;
+    return setup_hash_device(curve, d_msgs, n, d_u);
+}
+int mira_map_to_curve_device(int curve, const void *d_u, size_t n, void *d_points) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    if (!curve_ok(curve) || (n && (!d_u || !d_points)) || n > ((uint64_t)1 << 32)) { set_error("bad map_to_curve arguments"); return MIRA_E_BAD_ARG; }
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!n) return MIRA_OK;
+    return setup_map_device(curve, d_u, n, d_points);
 }
 
 int mira_dev_alloc(size_t bytes, void **d_out) {

@@ -113,7 +113,7 @@ struct Ctx {
     hipStream_t copy_stream = nullptr;   // host scalars travel here, chunk by chunk, beside the kernels of earlier chunks
     std::vector<hipEvent_t> copy_events;
     int32_t forced_c = 0;
-    int64_t tune[24] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // mira_set_tuning overrides, < 0 = default
+    int64_t tune[25] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // mira_set_tuning overrides, < 0 = default
     Timing tm;
     // MSM workspace (grow-only, shared by all handles: calls are serialised by the ABI lock)
     DevBuf digits, counts, offsets, cursor, block_sums, sorted_idx, bucket_sums, part, coarse_offsets, fine_counts, fine_cursor;
@@ -132,6 +132,7 @@ struct Ctx {
     DevBuf inv_ws;                   // batch inversion: upper levels' values and prefix products (lookup.hip)
     DevBuf lk_owner, lk_first, lk_count, lk_slot, lk_err;   // the multiplicities' hash table, every t element's slot, the error word
     DevBuf decide_parts, decide_eval, decide_inst;   // deciders (decide.hip): result + partial records, the row sweep's evaluation, the uploaded instance
+    DevBuf setup_stage;              // key setup (setup.hip): two chunks of stream bytes, uploaded beside the kernels
     uint32_t hist_host[256] = {};    // the statistics of the last commit that collected them
     int32_t last_c = 0, last_w = 0;  // mira_msm_last_plan
     int32_t last_table_c = 0;        // mira_msm_last_table_bits: width of the table set the last commit went through, 0 = none
@@ -313,6 +314,11 @@ int sum_sub_device(int field, const void *d_a, const void *d_b, size_t n, uint64
 int perm_compile(int field, const uint64_t *rows, const uint64_t *cols, const uint64_t *values, size_t nnz, size_t n, uint64_t *handle_out);
 int perm_check_device(uint64_t handle, const uint64_t *instance, size_t num_io, const void *d_w, size_t n_w, uint64_t *mismatch_out, uint64_t *first_out);
 int perm_free(uint64_t handle);
+
+// setup.hip
+int setup_hash_device(int curve, const void *d_msgs, size_t n, void *d_u);
+int setup_map_device(int curve, const void *d_u, size_t n, void *d_points);
+int setup_bases_device(int curve, const unsigned char *label, size_t label_len, uint64_t first, size_t n, void *d_out, bool resident);
 
 // graph.hip
 int graph_compile(int field, const mira_graph *gr, uint32_t num_challenges, uint32_t num_columns, uint64_t *handle_out);
