@@ -80,3 +80,11 @@ def fft_device(d_a, log_n, lib=None):
 def ifft_device(d_a, log_n, lib=None):
     lib = lib or _lib.load()
     lib.check(lib.c.mira_ifft_bn256_fr_device(ctypes.c_void_p(d_a), log_n))
+
+
+def best_fft_device(d_a, omega, log_n, lib=None):
+    """best_fft (src/fft.rs:51-115) in place on 2^log_n device elements at d_a"""
+    lib = lib or _lib.load()
+    assert log_n <= FR_S, f"k={log_n} should no larger than F::S={FR_S}"
+    omega = np.ascontiguousarray(omega, dtype=np.uint64)
+    lib.check(lib.c.mira_ntt_bn256_fr_device(ctypes.c_void_p(d_a), log_n, omega.ctypes.data_as(ctypes.c_void_p)))
