@@ -62,7 +62,15 @@ static inline hipError_t rt_stream_wait(hipStream_t waiter, hipStream_t done, hi
 typedef int hipEvent_t;
 static inline int rt_stream_wait(hipStream_t, hipStream_t, hipEvent_t) { return 0; }
 static inline int rt_event_sync(hipEvent_t) { return 0; }
-#define RT_CHECK(expr) do { (void)(expr); } while (0)
+// (every emulated runtime call below succeeds, but for an allocation that fails and for rt_wait_flag: a kernel that never stores the
+// stamp of its launch is an error here too)
+#define RT_CHECK(expr)                                                                     \
+    do {                                                                                   \
+        if ((expr) != 0) {                                                                 \
+            set_error(std::string(#expr) + " failed");                                     \
+            return MIRA_E_NO_DEVICE;                                                       \
+        }                                                                                  \
+    } while (0)
 static inline int rt_malloc(void **p, size_t n) { *p = aligned_alloc(64, (n + 63) / 64 * 64); return *p ? 0 : 1; }
 static inline int rt_free(void *p) { free(p); return 0; }
 static inline int rt_memset(void *p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }
