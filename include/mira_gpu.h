@@ -247,7 +247,8 @@ int mira_msm_tuning_import(uint64_t handle, const void *buf, size_t len, int32_t
 /* column reads a specialised cross-term kernel keeps in flight ahead of their use (mira_graph_specialize); default 4 */
 #define MIRA_TUNE_JIT_LOADS_AHEAD 9
 /* smallest number of sorted entries one lane of k_accumulate adds (shorter segments: more lanes busy on a small commit,
- * more cut runs for the fix-up); default 10 */
+ * more cut runs for the fix-up); 1 .. 2^20, default 10 (negative: the default; 0 and longer ones: MIRA_E_BAD_ARG -- the
+ * planner divides by it and keeps it in 32 bits) */
 #define MIRA_TUNE_MIN_SEGMENT 10
 /* 0: do not use a key's endomorphism copy (MIRA_TABLE_GLV) -- same-key A/B runs and tests; default 1 */
 #define MIRA_TUNE_GLV 11

@@ -483,6 +483,7 @@ int mira_set_tuning(int knob, int64_t value) {
     if (knob < 0 || knob > MIRA_TUNE_SETUP_CHUNK || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
     if (knob == MIRA_TUNE_DECIDE_GRID && (value == 0 || value > 2048)) { set_error("MIRA_TUNE_DECIDE_GRID takes 1 .. 2048 workgroups (negative: the default)"); return MIRA_E_BAD_ARG; }
     if (knob == MIRA_TUNE_SETUP_CHUNK && value >= 0 && (value < 16 || value > (1 << 24))) { set_error("MIRA_TUNE_SETUP_CHUNK takes 16 .. 2^24 points (negative: the default)"); return MIRA_E_BAD_ARG; }
+    if (knob == MIRA_TUNE_MIN_SEGMENT && (value == 0 || value > (1 << 20))) { set_error("MIRA_TUNE_MIN_SEGMENT takes 1 .. 2^20 entries (negative: the default)"); return MIRA_E_BAD_ARG; }
     g.tune[knob] = value;
     return MIRA_OK;
 }

@@ -415,9 +415,16 @@ DEV uint32_t acc_wave() { return threadIdx.x >> 6; }
 #else
 DEV uint32_t acc_wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 #endif
+#ifdef MIRA_CPU_EMU
+static thread_local const uint32_t *acc_emu_segment_end = nullptr;          // (emulation) where the running lane's segment ends
+#endif
 // the lane's entries src[0 .. ACC_STAGE) -> block `buf` of its wave's stage (buf is the same in every lane that calls this at once)
 DEV void acc_stage_block(uint32_t *wave_stage, uint32_t buf, const uint32_t *src) {
 #ifdef MIRA_CPU_EMU
+    // a memcpy cares for neither: the emulation holds the kernel to its own rules -- a block begins 16-byte aligned, and it holds at
+    // least one entry of the lane's segment (so it reaches at most ACC_STAGE - 1 entries past the sorted entries)
+    F29_ASSERT((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    F29_ASSERT(src < acc_emu_segment_end);
     for (uint32_t q = 0; q < ACC_STAGE / 4; q++) memcpy(wave_stage + buf * (64 * ACC_STAGE) + q * 256 + acc_lane() * 4, src + 4 * q, 16);
 #else
     uint32_t *dst = wave_stage + __builtin_amdgcn_readfirstlane(buf) * (64 * ACC_STAGE);
@@ -475,6 +482,9 @@ KERNEL void __launch_bounds__(ACC_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 3
 #if MSM_ACC_STAGE
     uint32_t *wave_stage = stage + acc_wave() * ACC_STAGE_WAVE_WORDS;
     const uint32_t stage_at = start & ~3u;                   // staged blocks begin 16-byte aligned
+#ifdef MIRA_CPU_EMU
+    acc_emu_segment_end = sorted + end;
+#endif
     acc_stage_block(wave_stage, 0, sorted + stage_at);
     if (stage_at + ACC_STAGE < end) acc_stage_block(wave_stage, 1, sorted + stage_at + ACC_STAGE);
 #endif
