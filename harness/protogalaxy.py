@@ -6,7 +6,8 @@ src/nifs/protogalaxy/poly/mod.rs:66-179, 218-303, 339-382), the Lagrange helpers
 The heavy parts run on the GPU through the C ABI: every gate over every row
 (`mira_graph_eval_device`), the folded witnesses (`mira_lincomb_device`), the weighted tree
 reduction over all gate evaluations (`mira_pow_tree_reduce_device`) and the small transforms
-(`mira_ifft_bn256_fr`, `mira_coset_*`).  What stays here is O(points) scalar arithmetic on Python
+(`mira_ifft_bn256_fr`, `mira_coset_*`) -- or, in `compute_G_fused`, one `mira_graph_eval_folded_reduce` in place
+of the first three for all of compute_G.  What stays here is O(points) scalar arithmetic on Python
 integers.  The field is bn256::Fr (the only one of the two with an FFT domain).
 
 Data model: `Structure` = the parts of `PlonkStructure` this path reads; a trace = `Trace`
@@ -211,6 +212,44 @@ def compute_G(S, betas_stroke, accumulator, traces, lib=None):
     return _ints(_ifft_small(values, log_points, lib))
 
 
+def compute_G_fused(S, betas_stroke, accumulator, traces, lib=None):
+    """compute_G with FoldedTrace created on the fly (the reference's own TODO, folded_trace.rs:69): one
+    `mira_graph_eval_folded_reduce` folds the witness columns inside the gate kernel's column fetch for every
+    evaluation point at once and reduces the leaves where they are computed.  Neither the folded witnesses nor the
+    leaves are written out.  What stays on the host is what `fold_traces` keeps there: the Lagrange coefficients and
+    the folded challenges, O(points) scalars.  Same coefficients as `compute_G`."""
+    lib = lib or _lib.load()
+    if not traces:
+        raise ValueError("You can't fold 0 traces")              # Error::EmptyTracesNotAllowed
+    rows, gates = 1 << S.k, len(S.gates)
+    count = rows * gates
+    if count == 0:
+        return []
+    points_count = 1 << (len(traces) * S.max_degree()).bit_length()
+    log_points = points_count.bit_length() - 1
+    levels = (count - 1).bit_length()
+    betas_stroke = list(betas_stroke)[:levels]
+    all_traces = [accumulator] + list(traces)
+    log_n = (len(all_traces) - 1).bit_length()                 # (len + 1).next_power_of_two().ilog2()
+    coeffs, challenges = [], []
+    for X in iter_cyclic_subgroup(log_points, lib):
+        L = eval_lagrange_poly_for_cyclic_group(X, log_n, lib)[: len(all_traces)]
+        coeffs.append(L)
+        challenges.append([sum(l * t.challenges[i] for l, t in zip(L, all_traces)) % R_MOD for i in range(len(accumulator.challenges))])
+    tables = [G.PlonkEvalDomain(S.num_advice, S.num_lookup, t.challenges, S.selectors, S.fixed, t.W, [], rows).columns() for t in all_traces]
+    shared = len(S.selectors) + len(S.fixed)
+    folded = [c >= shared for c in range(len(tables[0]))]
+    evaluators = [G.GraphEvaluator.new(gate, FIELD) for gate in S.gates]
+    try:
+        values = G.GraphEvaluator.evaluate_folded_reduce(evaluators, tables, folded, coeffs, challenges, rows, betas_stroke, lib=lib)
+    finally:
+        for ev in evaluators:
+            ev.close()
+    if log_points == 0:
+        return _ints(values)
+    return _ints(_ifft_small(values, log_points, lib))
+
+
 def beta_stroke(betas, alpha, delta):
     """BetaStrokeIter (:318-337): beta_i + alpha * delta^(2^i), delta doubling as the reference does"""
     out = []
@@ -221,9 +260,10 @@ def beta_stroke(betas, alpha, delta):
 
 
 # ---------------------------------------------------------------- compute_K (:339-382)
-def compute_K(S, f_alpha, betas_stroke, accumulator, traces, lib=None):
+def compute_K(S, f_alpha, betas_stroke, accumulator, traces, lib=None, fused=False):
+    """fused: G through `compute_G_fused` (same values)"""
     lib = lib or _lib.load()
-    g_poly = compute_G(S, betas_stroke, accumulator, traces, lib)
+    g_poly = (compute_G_fused if fused else compute_G)(S, betas_stroke, accumulator, traces, lib)
     points_count = 1 << (len(traces) * S.max_degree()).bit_length()
     log_n = points_count.bit_length() - 1
     from mira_amd import fft as F

@@ -295,6 +295,10 @@ int mira_msm_tuning_import(uint64_t handle, const void *buf, size_t len, int32_t
  * two pinned buffers while the kernels of the chunk before run; 16 .. 2^24, default 2^18 (anything else that is not negative ->
  * MIRA_E_BAD_ARG).  Tests set it small so that chunk boundaries fall inside the sponge's 136-byte blocks.  Never changes a result */
 #define MIRA_TUNE_SETUP_CHUNK 24
+/* row-block workgroups per (point, gate) of mira_graph_eval_folded_device / mira_graph_eval_folded_reduce: each walks the blocks of
+ * 256 rows b, b + value, ...; 0 or negative: the default (about 2048 workgroups over all points and gates, at most one per row
+ * block).  Tests use it to make one workgroup walk several row blocks at small sizes.  Never changes a result */
+#define MIRA_TUNE_FOLDED_GRID 25
 int mira_set_tuning(int knob, int64_t value);
 
 /* Read a range of the registered key back in the reference layout (cache file writing,
@@ -457,6 +461,42 @@ int mira_graph_jit_source(uint64_t handle, const mira_eval_column *columns, uint
 int mira_graph_set_cache_dir(const char *dir);
 int mira_graph_jit_stats(uint32_t *compiled_out, uint32_t *from_disk_out);
 int mira_graph_jit_compile_check(const char *source, size_t *code_size_out);
+
+/* ---- ProtoGalaxy's compute_G: the gates of a circuit over a Lagrange combination of traces ----------------------------
+ * compute_G (src/nifs/protogalaxy/poly/mod.rs:218-303) evaluates every gate over every row of FoldedTrace(X_p) for every
+ * evaluation point X_p and reduces the values through a weighted tree.  The reference materialises a folded trace per point
+ * (folded_trace.rs:69: "TODO Create on the fly to avoid multiple rows iterations"); here the fold happens in the column
+ * fetch of the interpreter and, in the reduce form, the leaves never leave the workgroup.
+ *
+ * handles[g], g < num_gates: compiled graphs (mira_graph_compile) of one field, all compiled for num_columns / num_challenges:
+ *   S.gates in the order of plonk::iter_evaluate_witness (src/plonk/mod.rs:1158-1178).
+ * columns[j * num_columns + c]: column c of trace j, j < num_traces (trace 0 = the accumulator), 1 <= num_traces <= 16.
+ * column_folded[c] != 0: a witness column -- the value the program reads at (c, row) is
+ *       sum_j coeffs[p * num_traces + j] * columns[j][c][row]          (FoldedTrace, folded_trace.rs:53-131)
+ *   and must be MIRA_COL_FIELD in every trace;  == 0: a column of the circuit (selector, fixed): read from trace 0 as it is.
+ * coeffs: host, num_points x num_traces elements, Montgomery: L_j(X_p).  challenges: host, num_points x num_challenges,
+ *   the caller's fold_plonk_challenges (:135-179: O(points) scalar work, it stays with the caller).
+ * 1 <= num_points <= 256.
+ * Every value equals the one mira_lincomb_device + mira_graph_eval_compiled (+ mira_pow_tree_reduce_device) give, bit for bit.
+ * Errors: an unknown handle, graphs of different fields or compiled for other column / challenge counts, a null column that
+ * some gate reads (in any trace for a folded column: "column variable index out of boundary"), a folded column of kind
+ * MIRA_COL_BOOL, num_traces or num_points out of range -> MIRA_E_BAD_ARG; num_rows > 2^31 -> MIRA_E_UNSUPPORTED; nothing is
+ * written then.  num_rows == 0: success (`out` all zero).  A gate with no calculations contributes zero leaves.
+ * A handle with a specialised kernel (mira_graph_specialize) is INTERPRETED by these two calls: the generated kernels read
+ * plain columns only.  MIRA_TUNE_FOLDED_GRID sets the workgroups per (point, gate). */
+int mira_graph_eval_folded_device(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns,
+                                  uint32_t num_traces, const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges,
+                                  uint32_t num_challenges, uint32_t num_points, size_t num_rows,
+                                  void *d_out /* [(p * num_gates + g) * num_rows + row], canonical Montgomery */);
+/* The same evaluation reduced through compute_G's tree (:263-290) without writing the leaves:
+ *   out[p] = sum_i leaf[p][i] * prod_{j : bit j of i} weights[j],  i = g * num_rows + row,  levels = log2(num_gates * num_rows)
+ * weights: host, `levels` elements (betas_stroke, the same for every point).  out: host, num_points elements.
+ * num_gates * num_rows not a power of two -> MIRA_E_UNSUPPORTED (the reference's tree is `unreachable!` there).
+ * A workgroup folds the first min(8, log2 num_rows) levels of its 256 rows in LDS; one node per (point, gate, row block) goes to
+ * library scratch (released by mira_trim) and the rounds of mira_pow_tree_reduce_device finish from there. */
+int mira_graph_eval_folded_reduce(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns,
+                                  uint32_t num_traces, const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges,
+                                  uint32_t num_challenges, uint32_t num_points, size_t num_rows, const uint64_t *weights, uint64_t *out);
 
 /* ---- the deciders on device-resident vectors (src/plonk/mod.rs:434-622) ------------------------
  * What IVC::verify (src/ivc/incrementally_verifiable_computation.rs:617-680) runs over the witness vectors a fold step left

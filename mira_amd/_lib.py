@@ -35,6 +35,7 @@ SYMBOLS = [
     "mira_batch_invert_device", "mira_lookup_m_device", "mira_lookup_h_g_device",
     "mira_count_ne_device", "mira_sum_sub_device", "mira_graph_check_compiled", "mira_perm_compile", "mira_perm_check_device", "mira_perm_free",
     "mira_setup_bases_device", "mira_msm_setup_bases", "mira_hash_to_field_device", "mira_map_to_curve_device",
+    "mira_graph_eval_folded_device", "mira_graph_eval_folded_reduce",
 ]
 TUNE_STAGED_MIN_N, TUNE_TABLE_MIN_N, TUNE_PLAN_HIST_MIN_N, TUNE_NTT_MAX_LOG_LINE, TUNE_NTT_WAVE, TUNE_HOST_CHUNK_MIN_N, TUNE_NTT_SINGLE_TW_LOG, TUNE_NTT_FULL_TW_MAX_LOG, TUNE_TABLE_WIDTH, TUNE_JIT_LOADS_AHEAD, TUNE_MIN_SEGMENT, TUNE_GLV = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 TUNE_REDUCE_PIECES, TUNE_REDUCE_LAMBDA, TUNE_REDUCE_QUAD, TUNE_SHARED_MIN_N, TUNE_PASS_ENTRIES_LOG, TUNE_GLV_AUTO_MAX_LOG, TUNE_WIDTH_TRIALS = 12, 13, 14, 15, 16, 17, 18
@@ -43,6 +44,7 @@ TUNE_WIDE_FRONT_MIN_C = 20
 TUNE_LOOKUP_HASH, TUNE_INV_CHUNK = 21, 22
 TUNE_DECIDE_GRID = 23
 TUNE_SETUP_CHUNK = 24
+TUNE_FOLDED_GRID = 25
 TABLE_GLV = 2   # mira_msm_precompute_ex(handle, MIRA_TABLE_GLV): the endomorphism copy of a key
 
 
@@ -137,6 +139,8 @@ class MiraLib:
             "mira_perm_compile": [ctypes.c_int, u64p, u64p, u64p, sz, sz, vp], "mira_perm_check_device": [u64, u64p, sz, vp, sz, vp, vp], "mira_perm_free": [u64],
             "mira_setup_bases_device": [ctypes.c_int, ctypes.c_char_p, sz, u64, sz, vp], "mira_msm_setup_bases": [ctypes.c_int, u32, ctypes.c_char_p, sz, vp],
             "mira_hash_to_field_device": [ctypes.c_int, vp, sz, vp], "mira_map_to_curve_device": [ctypes.c_int, vp, sz, vp],
+            "mira_graph_eval_folded_device": [vp, u32, vp, u32, u32, vp, u64p, u64p, u32, u32, sz, vp],
+            "mira_graph_eval_folded_reduce": [vp, u32, vp, u32, u32, vp, u64p, u64p, u32, u32, sz, u64p, u64p],
         }
         for name, args in sig.items():
             fn = getattr(c, name)

@@ -480,7 +480,7 @@ int mira_msm_combine(int curve, const uint64_t *partials, size_t nparts, int32_t
 }
 int mira_set_tuning(int knob, int64_t value) {
     std::lock_guard<std::mutex> lk(g_lock);
-    if (knob < 0 || knob > MIRA_TUNE_SETUP_CHUNK || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
+    if (knob < 0 || knob > MIRA_TUNE_FOLDED_GRID || (knob == MIRA_TUNE_PASS_ENTRIES_LOG && value > 32)) { set_error("unknown tuning knob"); return MIRA_E_BAD_ARG; }
     if (knob == MIRA_TUNE_DECIDE_GRID && (value == 0 || value > 2048)) { set_error("MIRA_TUNE_DECIDE_GRID takes 1 .. 2048 workgroups (negative: the default)"); return MIRA_E_BAD_ARG; }
     if (knob == MIRA_TUNE_SETUP_CHUNK && value >= 0 && (value < 16 || value > (1 << 24))) { set_error("MIRA_TUNE_SETUP_CHUNK takes 16 .. 2^24 points (negative: the default)"); return MIRA_E_BAD_ARG; }
     if (knob == MIRA_TUNE_MIN_SEGMENT && (value == 0 || value > (1 << 20))) { set_error("MIRA_TUNE_MIN_SEGMENT takes 1 .. 2^20 entries (negative: the default)"); return MIRA_E_BAD_ARG; }
@@ -652,7 +652,7 @@ int mira_trim(size_t keep_bytes, size_t *released_out) {
     // `consts`, `ntt_consts` and `fold_consts` hold uploaded constants (a few hundred bytes): never released
     std::vector<DevBuf *> bufs = {&g.digits, &g.counts, &g.offsets, &g.cursor, &g.block_sums, &g.sorted_idx, &g.bucket_sums, &g.part, &g.coarse_offsets,
                                   &g.fine_counts, &g.fine_cursor, &g.head_part, &g.tail_part, &g.tail_key, &g.heavy, &g.heavy_out, &g.chunks, &g.window_sums,
-                                  &g.scalars_stage, &g.ntt_tmp, &g.ntt_stage, &g.graph_ws, &g.tree_a, &g.tree_b, &g.hist_dev,
+                                  &g.scalars_stage, &g.ntt_tmp, &g.ntt_stage, &g.graph_ws, &g.fold_nodes, &g.tree_a, &g.tree_b, &g.hist_dev,
                                   &g.inv_ws, &g.lk_owner, &g.lk_first, &g.lk_count, &g.lk_slot, &g.decide_parts, &g.decide_eval, &g.decide_inst, &g.setup_stage};
     for (int i = 0; i < Ctx::NTT_SETS; i++) bufs.push_back(&g.ntt_set[i]);
     size_t total = 0;
@@ -932,6 +932,40 @@ int mira_graph_eval_batch(const uint64_t *handles, uint32_t count, const mira_ev
     if (rc) return rc;
     if ((count && (!handles || !d_outs)) || (num_columns && !columns) || (num_challenges && !challenges)) { set_error("bad graph evaluation arguments"); return MIRA_E_BAD_ARG; }
     return graph_eval_batch(handles, count, columns, num_columns, challenges, num_challenges, num_rows, d_outs);
+}
+static bool folded_args_ok(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns, uint32_t num_traces,
+                           const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges, uint32_t num_challenges, uint32_t num_points) {
+    if (num_traces < 1 || num_traces > 16) { set_error("num_traces must be 1 .. 16"); return false; }
+    if (num_points < 1 || num_points > 256) { set_error("num_points must be 1 .. 256"); return false; }
+    if ((num_gates && !handles) || (num_columns && (!columns || !column_folded)) || !coeffs || (num_challenges && !challenges)) {
+        set_error("bad folded graph evaluation arguments");
+        return false;
+    }
+    return true;
+}
+int mira_graph_eval_folded_device(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns, uint32_t num_traces,
+                                  const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges, uint32_t num_challenges, uint32_t num_points,
+                                  size_t num_rows, void *d_out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!folded_args_ok(handles, num_gates, columns, num_columns, num_traces, column_folded, coeffs, challenges, num_challenges, num_points)) return MIRA_E_BAD_ARG;
+    if (num_rows && num_gates && !d_out) { set_error("null output"); return MIRA_E_BAD_ARG; }
+    return graph_eval_folded(handles, num_gates, columns, num_columns, num_traces, column_folded, coeffs, challenges, num_challenges, num_points, num_rows, d_out, nullptr, nullptr);
+}
+int mira_graph_eval_folded_reduce(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns, uint32_t num_traces,
+                                  const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges, uint32_t num_challenges, uint32_t num_points,
+                                  size_t num_rows, const uint64_t *weights, uint64_t *out) {
+    std::lock_guard<std::mutex> lk(g_lock);
+    int rc = ensure_ctx();
+    if (rc) return rc;
+    if (!folded_args_ok(handles, num_gates, columns, num_columns, num_traces, column_folded, coeffs, challenges, num_challenges, num_points)) return MIRA_E_BAD_ARG;
+    if (!out) { set_error("null output"); return MIRA_E_BAD_ARG; }
+    static const uint64_t no_weights[4] = {0, 0, 0, 0};         // a tree of one leaf has no levels: `weights` may be null there
+    const size_t leaves = (size_t)num_gates * num_rows;
+    if (leaves > 1 && !weights) { set_error("null weights"); return MIRA_E_BAD_ARG; }
+    return graph_eval_folded(handles, num_gates, columns, num_columns, num_traces, column_folded, coeffs, challenges, num_challenges, num_points, num_rows, nullptr,
+                             weights ? weights : no_weights, out);
 }
 int mira_graph_free(uint64_t handle) {
     std::lock_guard<std::mutex> lk(g_lock);

@@ -121,7 +121,7 @@ struct Ctx {
     hipStream_t copy_stream = nullptr;   // host scalars travel here, chunk by chunk, beside the kernels of earlier chunks
     std::vector<hipEvent_t> copy_events;
     int32_t forced_c = 0;
-    int64_t tune[25] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // mira_set_tuning overrides, < 0 = default
+    int64_t tune[26] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // mira_set_tuning overrides, < 0 = default
     Timing tm;
     // MSM workspace (grow-only, shared by all handles: calls are serialised by the ABI lock)
     DevBuf digits, counts, offsets, cursor, block_sums, sorted_idx, bucket_sums, part, coarse_offsets, fine_counts, fine_cursor;
@@ -135,6 +135,7 @@ struct Ctx {
     int ntt_set_cur = 0;
     DevBuf fold_consts;
     DevBuf graph_consts, graph_ws;
+    DevBuf fold_nodes;               // folded gate evaluation (graph.hip): one tree node per (point, gate, row block), written by the call before it is read
     DevBuf hist_dev;
     DevBuf tree_w, tree_a, tree_b;   // weighted tree reduction: level weights, ping-pong partial results
     DevBuf inv_ws;                   // batch inversion: upper levels' values and prefix products (lookup.hip)
@@ -310,6 +311,8 @@ void to_mult48(int field, const uint64_t v_r256[4], uint32_t out[12]);   // refe
 int lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint64_t *coeffs, size_t K, size_t n);
 int lincomb_multi_device(int field, void *const *d_outs, size_t M, const void *const *d_vecs, size_t J, const uint64_t *coeffs, size_t n);
 int pow_tree_reduce_device(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out);
+int pow_tree_stage(uint32_t levels, const uint64_t *weights, uint32_t P);   // levels >= 1: workspaces and weights [P][levels] of the rounds below
+int pow_tree_launch(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, uint32_t P, const void **roots);   // enqueues only; point p's root: element p of *roots
 
 // lookup.hip
 int batch_invert_device(int field, void *d_out, const void *d_in, size_t n);
@@ -341,6 +344,10 @@ int graph_specialize(const uint64_t *handles, uint32_t count, const mira_eval_co
 int graph_is_specialized(uint64_t handle, int32_t *out);
 int graph_jit_stats(uint32_t *compiled_out, uint32_t *from_disk_out);
 int graph_jit_source(uint64_t handle, const mira_eval_column *columns, uint32_t num_columns, char *buf, size_t cap, size_t *len_out);
+// the gates of a circuit over a Lagrange combination of traces; weights == null: the leaves to d_out, else the tree's roots to `out` (host)
+int graph_eval_folded(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns, uint32_t num_traces,
+                      const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges, uint32_t num_challenges, uint32_t num_points, size_t num_rows,
+                      void *d_out, const uint64_t *weights, uint64_t *out);
 int graph_eval_device(int field, const mira_graph *gr, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges,
                       uint32_t num_challenges, size_t num_rows, void *d_out);
 // graph_jit.hip

@@ -147,21 +147,22 @@ int lincomb_device(int field, void *d_out, const void *const *d_vecs, const uint
 
 // Rounds of k_pow_tree until one value per point is left: each round folds up to 11 levels
 // (8 leaves per lane, 256 lanes per workgroup).
-template <class FP> static int pow_tree_t(const void *d_leaves, uint32_t levels_total, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out) {
+// In two halves of a tree reduction of levels_total >= 1 levels, so that a caller with kernels of its own in front of the tree
+// (graph.hip: the folded gate evaluation) keeps them in one timed submission: pow_tree_stage sizes the workspaces and uploads the
+// weights, pow_tree_launch enqueues the rounds and hands back where point p's root will lie (element p of *roots).
+int pow_tree_stage(uint32_t levels_total, const uint64_t *weights, uint32_t P) {
     int rc;
     const size_t n = (size_t)1 << levels_total;
-    if (levels_total == 0) {                                  // a single leaf per point is its own root
-        for (uint32_t p = 0; p < P; p++) RT_CHECK(rt_d2h(out + 4 * p, reinterpret_cast<const unsigned char *>(d_leaves) + (size_t)p * leaf_point_stride * 32, 32, g.stream));
-        RT_CHECK(rt_sync(g.stream));
-        return MIRA_OK;
-    }
     const size_t wbytes = (size_t)P * levels_total * 32;
     const size_t first_out = n >> std::min<uint32_t>(levels_total, 11);
     if ((rc = g.tree_w.ensure(wbytes))) return rc;
     if ((rc = g.tree_a.ensure(std::max<size_t>(1, first_out) * P * 32))) return rc;
     if ((rc = g.tree_b.ensure(std::max<size_t>(1, first_out >> std::min<size_t>(11, levels_total > 11 ? levels_total - 11 : 0)) * P * 32 + 32))) return rc;
     RT_CHECK(rt_h2d(g.tree_w.p, weights, wbytes, g.stream));
-    tm_begin();
+    return MIRA_OK;
+}
+template <class FP> static int pow_tree_launch_t(const void *d_leaves, uint32_t levels_total, size_t leaf_point_stride, uint32_t P, const void **roots) {
+    const size_t n = (size_t)1 << levels_total;
     const unsigned char *in = reinterpret_cast<const unsigned char *>(d_leaves);
     uint64_t in_stride = leaf_point_stride;
     uint32_t level0 = 0;
@@ -177,12 +178,29 @@ template <class FP> static int pow_tree_t(const void *d_leaves, uint32_t levels_
                        (const unsigned char *)g.tree_w.p, levels_total, bufs[which], (uint64_t)n_out);
         in = bufs[which]; in_stride = n_out; n_cur = n_out; level0 += levels; which ^= 1;
     }
+    *roots = in;                                             // n_cur == 1: point p's root at element p
+    return MIRA_OK;
+}
+template <class FP> static int pow_tree_t(const void *d_leaves, uint32_t levels_total, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out) {
+    int rc;
+    if (levels_total == 0) {                                  // a single leaf per point is its own root
+        for (uint32_t p = 0; p < P; p++) RT_CHECK(rt_d2h(out + 4 * p, reinterpret_cast<const unsigned char *>(d_leaves) + (size_t)p * leaf_point_stride * 32, 32, g.stream));
+        RT_CHECK(rt_sync(g.stream));
+        return MIRA_OK;
+    }
+    if ((rc = pow_tree_stage(levels_total, weights, P))) return rc;
+    tm_begin();
+    const void *roots = nullptr;
+    if ((rc = pow_tree_launch_t<FP>(d_leaves, levels_total, leaf_point_stride, P, &roots))) return rc;
     tm_mark("pow_tree");
     RT_CHECK(rt_last());
-    RT_CHECK(rt_d2h(out, in, (size_t)P * 32, g.stream));     // n_cur == 1: point p's root at element p
+    RT_CHECK(rt_d2h(out, roots, (size_t)P * 32, g.stream));
     RT_CHECK(rt_sync(g.stream));
     tm_end();
     return MIRA_OK;
+}
+int pow_tree_launch(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, uint32_t P, const void **roots) {
+    return field == 1 ? pow_tree_launch_t<FrP>(d_leaves, levels, leaf_point_stride, P, roots) : pow_tree_launch_t<FqP>(d_leaves, levels, leaf_point_stride, P, roots);
 }
 int pow_tree_reduce_device(int field, const void *d_leaves, uint32_t levels, size_t leaf_point_stride, const uint64_t *weights, uint32_t P, uint64_t *out) {
     return field == 1 ? pow_tree_t<FrP>(d_leaves, levels, leaf_point_stride, weights, P, out) : pow_tree_t<FqP>(d_leaves, levels, leaf_point_stride, weights, P, out);

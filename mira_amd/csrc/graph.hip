@@ -251,6 +251,187 @@ int graph_eval_batch(const uint64_t *handles, uint32_t count, const mira_eval_co
     return MIRA_OK;
 }
 
+// ---- the gates of a circuit over a Lagrange combination of traces (k_graph_eval_folded) ----------------------------------
+// Lanes of a workgroup: the emulation's are OS threads that meet at every barrier of the in-workgroup tree, so it takes small
+// workgroups (as REDUCE_SMALL_WG does); the kernel is written for any power of two up to 256.
+#ifdef MIRA_CPU_EMU
+static constexpr uint32_t FOLDED_BLOCK = 32, FOLDED_BLOCK_LOG = 5;
+#else
+static constexpr uint32_t FOLDED_BLOCK = 256, FOLDED_BLOCK_LOG = 8;
+#endif
+static constexpr uint32_t FOLDED_WORKGROUPS = 2048;   // default grid over all (point, gate, row block): a few turns of the two 80 KiB workgroups a CU's LDS holds
+
+template <class F, bool REDUCE>
+static void launch_folded(dim3 grid, size_t lds_bytes, const GraphJob *jobs, const GraphCol *cols, uint32_t ncols, uint32_t ntraces, const unsigned char *coeffs,
+                          uint64_t nrows, uint32_t *ws, uint64_t ws_stride, const unsigned char *w, uint32_t tree_levels) {
+    if (REDUCE) LAUNCH_BARRIER((k_graph_eval_folded<F, REDUCE>), grid, FOLDED_BLOCK, lds_bytes, g.stream, jobs, cols, ncols, ntraces, coeffs, nrows, ws, ws_stride, w, tree_levels);
+    else LAUNCH((k_graph_eval_folded<F, REDUCE>), grid, FOLDED_BLOCK, lds_bytes, g.stream, jobs, cols, ncols, ntraces, coeffs, nrows, ws, ws_stride, w, tree_levels);
+}
+
+// weights == null: the leaves go to d_out[(p * num_gates + g) * num_rows + row].  Else: the roots of compute_G's tree to out[p]
+// (host); the first min(log2 FOLDED_BLOCK, log2 num_rows) levels are folded inside the workgroups, the nodes lie in g.fold_nodes
+// as k_pow_tree expects its leaves (node index = leaf index >> levels, point stride num_gates * num_rows >> levels).
+// A specialised handle (mira_graph_specialize) is interpreted here: the generated kernels know plain columns only.
+int graph_eval_folded(const uint64_t *handles, uint32_t num_gates, const mira_eval_column *columns, uint32_t num_columns, uint32_t num_traces,
+                      const uint8_t *column_folded, const uint64_t *coeffs, const uint64_t *challenges, uint32_t num_challenges, uint32_t num_points, size_t num_rows,
+                      void *d_out, const uint64_t *weights, uint64_t *out) {
+    int rc;
+    const bool reduce = weights != nullptr;
+    std::vector<Program *> pgs(num_gates);
+    for (uint32_t k = 0; k < num_gates; k++) {
+        auto it = g_programs.find(handles[k]);
+        if (it == g_programs.end()) { set_error("unknown graph handle"); return MIRA_E_BAD_ARG; }
+        Program &pg = *(pgs[k] = &it->second);
+        if (num_challenges != pg.num_challenges || num_columns != pg.num_columns) {
+            set_error("the graph was compiled for " + std::to_string(pg.num_challenges) + " challenges and " + std::to_string(pg.num_columns) + " columns");
+            return MIRA_E_BAD_ARG;
+        }
+        if (pg.field != pgs[0]->field) { set_error("the graphs of a batch must be over one field"); return MIRA_E_BAD_ARG; }
+        for (uint32_t col : pg.cg.used_columns) {
+            for (uint32_t j = 0; j < (column_folded[col] ? num_traces : 1u); j++) {
+                const mira_eval_column &c = columns[(size_t)j * num_columns + col];
+                if (!c.d_data) {
+                    set_error("column variable index out of boundary: " + std::to_string(col) + (j ? " of trace " + std::to_string(j) : std::string()));
+                    return MIRA_E_BAD_ARG;
+                }
+                if (c.kind != MIRA_COL_FIELD && c.kind != MIRA_COL_BOOL) { set_error("unknown column kind"); return MIRA_E_BAD_ARG; }
+                if (column_folded[col] && c.kind != MIRA_COL_FIELD) { set_error("folded column " + std::to_string(col) + " is not of kind MIRA_COL_FIELD"); return MIRA_E_BAD_ARG; }
+            }
+        }
+    }
+    if (num_rows > ((size_t)1 << 31)) { set_error("num_rows > 2^31"); return MIRA_E_UNSUPPORTED; }
+    const size_t leaves = (size_t)num_gates * num_rows;
+    if (reduce && leaves == 0) { memset(out, 0, (size_t)num_points * 32); return MIRA_OK; }
+    if (leaves == 0) return MIRA_OK;
+    uint32_t levels_total = 0, rows_log = 0;
+    if (reduce) {
+        if (leaves & (leaves - 1)) {
+            set_error("tree reduction needs a power-of-two number of leaves, got " + std::to_string(num_gates) + " gates x " + std::to_string(num_rows) + " rows");
+            return MIRA_E_UNSUPPORTED;
+        }
+        while (((size_t)1 << levels_total) < leaves) levels_total++;
+        while (((size_t)1 << rows_log) < num_rows) rows_log++;
+    }
+    const uint32_t block = FOLDED_BLOCK, tree_levels = reduce ? std::min(FOLDED_BLOCK_LOG, rows_log) : 0, tail_levels = levels_total - tree_levels;
+    const size_t nblocks = (num_rows + block - 1) / block;
+    const size_t nodes_per_point = leaves >> tree_levels;                 // reduce: node index = leaf index >> tree_levels
+    Program &p0 = *pgs[0];                                   // its staging carries the call's tables
+    const int field = p0.field;
+    // the largest launch: gates per launch, challenge entries per point
+    size_t worst_chal = 0;
+    for (uint32_t done = 0; done < num_gates; done += GRAPH_MAX_BATCH) {
+        size_t wv = 0;
+        for (uint32_t k = done; k < std::min<uint32_t>(num_gates, done + GRAPH_MAX_BATCH); k++) wv += pgs[k]->cg.chal_vars.size();
+        worst_chal = std::max(worst_chal, wv);
+    }
+    const uint32_t max_cnt = std::min<uint32_t>(num_gates, GRAPH_MAX_BATCH);
+    // staging of one launch: column tables of every trace (the folded flag in trace 0's) | job per (point, gate) | coefficients
+    // per (point, trace), multiplier form | the tree's first weights | challenges per (point, gate) in the forms the program reads
+    const size_t o_cols = 0;
+    const size_t o_jobs = align16((size_t)num_traces * num_columns * sizeof(GraphCol));
+    const size_t o_coef = align16(o_jobs + (size_t)num_points * max_cnt * sizeof(GraphJob));
+    const size_t o_w = o_coef + (size_t)num_points * num_traces * 48;
+    const size_t o_chal = o_w + (size_t)FOLDED_BLOCK_LOG * 32;
+    const size_t total = o_chal + ((size_t)num_points * worst_chal + 1) * 36;
+    if ((rc = ensure_dyn(p0, total))) return rc;
+    if (reduce && (rc = g.fold_nodes.ensure((size_t)num_points * nodes_per_point * 32))) return rc;
+    std::vector<uint64_t> tail_w;
+    if (reduce && tail_levels) {                             // k_pow_tree takes weights per point
+        tail_w.resize((size_t)num_points * tail_levels * 4);
+        for (uint32_t p = 0; p < num_points; p++) memcpy(tail_w.data() + (size_t)p * tail_levels * 4, weights + (size_t)tree_levels * 4, (size_t)tail_levels * 32);
+        if ((rc = pow_tree_stage(tail_levels, tail_w.data(), num_points))) return rc;
+    }
+    for (uint32_t j = 0; j < num_traces; j++)
+        for (uint32_t c = 0; c < num_columns; c++) {
+            const mira_eval_column &col = columns[(size_t)j * num_columns + c];
+            GraphCol gc{reinterpret_cast<const unsigned char *>(col.d_data), col.kind, j == 0 && column_folded[c] ? 1u : 0u};
+            memcpy(p0.h_dyn + o_cols + ((size_t)j * num_columns + c) * sizeof(GraphCol), &gc, sizeof gc);
+        }
+    for (size_t q = 0; q < (size_t)num_points * num_traces; q++) to_mult48(field, coeffs + q * 4, reinterpret_cast<uint32_t *>(p0.h_dyn + o_coef + q * 48));
+    if (tree_levels) memcpy(p0.h_dyn + o_w, weights, (size_t)tree_levels * 32);
+    size_t want_grid = tuned(MIRA_TUNE_FOLDED_GRID, 0);
+    if (want_grid == 0) want_grid = std::max<size_t>(1, FOLDED_WORKGROUPS / ((size_t)num_points * max_cnt));
+    const uint32_t gx = (uint32_t)std::min<size_t>(nblocks, want_grid);
+    const size_t T = (size_t)gx * block;
+#ifndef MIRA_CPU_EMU
+    static bool lds_ready = false;                           // eight LDS slots and the tree's nodes are 80 KiB, above the 64 KiB default
+    if (!lds_ready) {
+        const int most = (int)(GRAPH_LDS_SLOTS_LONE * 9 * block * 4 + FOLDED_TREE_BYTES);
+        RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_graph_eval_folded<Fq29, false>), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_graph_eval_folded<Fr29, false>), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_graph_eval_folded<Fq29, true>), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        RT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_graph_eval_folded<Fr29, true>), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        lds_ready = true;
+    }
+#endif
+    unsigned char *dst = reinterpret_cast<unsigned char *>(reduce ? g.fold_nodes.p : d_out);
+    const size_t per_gate = reduce ? num_rows >> tree_levels : num_rows;   // elements one (point, gate) writes
+    tm_begin();
+    for (uint32_t done = 0; done < num_gates; done += GRAPH_MAX_BATCH) {
+        const uint32_t cnt = std::min<uint32_t>(GRAPH_MAX_BATCH, num_gates - done);
+        if (done) RT_CHECK(rt_sync(g.stream));               // the previous launch's copy still reads the pinned staging
+        std::vector<uint32_t> live;                          // gates of this launch that have calculations
+        uint32_t max_slots = 1, max_nlds = 0;
+        for (uint32_t k = 0; k < cnt; k++) {
+            Program &pg = *pgs[done + k];
+            if (pg.num_calculations == 0) {                  // Ok(F::ZERO), graph_evaluator.rs:386-389: zero leaves, zero nodes
+                for (uint32_t p = 0; p < num_points; p++)
+                    RT_CHECK(rt_memset(dst + ((size_t)p * num_gates + done + k) * per_gate * 32, 0, per_gate * 32, g.stream));
+                continue;
+            }
+            live.push_back(done + k);
+            max_slots = std::max(max_slots, pg.cg.nslots);
+            max_nlds = std::max(max_nlds, std::min<uint32_t>(pg.cg.nslots, GRAPH_LDS_SLOTS_LONE));
+        }
+        if (live.empty()) continue;
+        const uint32_t nlive = (uint32_t)live.size();
+        size_t chal_at = 0;
+        const unsigned char *dy = reinterpret_cast<const unsigned char *>(p0.dyn.p);
+        for (uint32_t p = 0; p < num_points; p++)
+            for (uint32_t q = 0; q < nlive; q++) {
+                Program &pg = *pgs[live[q]];
+                const unsigned char *st = reinterpret_cast<const unsigned char *>(pg.d_static);
+                for (size_t v = 0; v < pg.cg.chal_vars.size(); v++)
+                    to_limbs29(field, challenges + ((size_t)p * num_challenges + pg.cg.chal_vars[v].first) * 4, pg.cg.chal_vars[v].second,
+                               reinterpret_cast<uint32_t *>(p0.h_dyn + o_chal) + (chal_at + v) * 9);
+                GraphJob job{reinterpret_cast<const uint32_t *>(st + pg.o_code), reinterpret_cast<const uint32_t *>(st + pg.o_const),
+                             reinterpret_cast<const uint32_t *>(dy + o_chal) + chal_at * 9, reinterpret_cast<const int32_t *>(st + pg.o_rot),
+                             dst + ((size_t)p * num_gates + live[q]) * per_gate * 32, pg.cg.ninstr, std::min<uint32_t>(pg.cg.nslots, GRAPH_LDS_SLOTS_LONE)};
+                memcpy(p0.h_dyn + o_jobs + ((size_t)p * nlive + q) * sizeof(GraphJob), &job, sizeof job);
+                chal_at += pg.cg.chal_vars.size();
+            }
+        RT_CHECK(rt_h2d(p0.dyn.p, p0.h_dyn, total, g.stream));
+        // slots past the LDS planes live in the workspace, indexed by slot like k_graph_eval's: none when every program fits LDS
+        const size_t ws_stride = max_slots > GRAPH_LDS_SLOTS_LONE ? (size_t)max_slots * 9 * T : 0;
+        if ((rc = g.graph_ws.ensure(std::max<size_t>(16, ws_stride * nlive * num_points * 4)))) return rc;
+        const dim3 grid(gx, nlive, num_points);
+        const size_t lds_bytes = (size_t)FOLDED_TREE_BYTES + (size_t)max_nlds * 9 * block * 4;
+        const GraphJob *jobs = reinterpret_cast<const GraphJob *>(dy + o_jobs);
+        const GraphCol *cols = reinterpret_cast<const GraphCol *>(dy + o_cols);
+        uint32_t *ws = reinterpret_cast<uint32_t *>(g.graph_ws.p);
+        if (field == MIRA_FIELD_FQ) {
+            if (reduce) launch_folded<Fq29, true>(grid, lds_bytes, jobs, cols, num_columns, num_traces, dy + o_coef, (uint64_t)num_rows, ws, (uint64_t)ws_stride, dy + o_w, tree_levels);
+            else launch_folded<Fq29, false>(grid, lds_bytes, jobs, cols, num_columns, num_traces, dy + o_coef, (uint64_t)num_rows, ws, (uint64_t)ws_stride, dy + o_w, tree_levels);
+        } else {
+            if (reduce) launch_folded<Fr29, true>(grid, lds_bytes, jobs, cols, num_columns, num_traces, dy + o_coef, (uint64_t)num_rows, ws, (uint64_t)ws_stride, dy + o_w, tree_levels);
+            else launch_folded<Fr29, false>(grid, lds_bytes, jobs, cols, num_columns, num_traces, dy + o_coef, (uint64_t)num_rows, ws, (uint64_t)ws_stride, dy + o_w, tree_levels);
+        }
+    }
+    tm_mark("graph_eval_folded");
+    if (reduce) {
+        const void *roots = g.fold_nodes.p;                  // no level left: the nodes are the roots, one per point
+        if (tail_levels && (rc = pow_tree_launch(field, g.fold_nodes.p, tail_levels, nodes_per_point, num_points, &roots))) return rc;
+        tm_mark("pow_tree");
+        RT_CHECK(rt_last());
+        RT_CHECK(rt_d2h(out, roots, (size_t)num_points * 32, g.stream));
+    } else {
+        RT_CHECK(rt_last());
+    }
+    RT_CHECK(rt_sync(g.stream));
+    tm_end();
+    return MIRA_OK;
+}
+
 int graph_eval_compiled(uint64_t handle, const mira_eval_column *columns, uint32_t num_columns, const uint64_t *challenges, uint32_t num_challenges,
                         size_t num_rows, void *d_out) {
     return graph_eval_batch(&handle, 1, columns, num_columns, challenges, num_challenges, num_rows, &d_out);

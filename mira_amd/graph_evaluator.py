@@ -161,6 +161,45 @@ class GraphEvaluator:
         return cols
 
     @staticmethod
+    def _folded_args(evaluators, trace_columns, folded, coeffs, challenges_by_point, lib):
+        """the arguments mira_graph_eval_folded_* share, up to num_points.  trace_columns[j]: the column table of trace j (trace 0 =
+        the accumulator), as for `evaluate_device`; folded[c]: column c is a witness column; coeffs[p][j], challenges_by_point[p][i]: ints"""
+        num_traces, num_columns, num_points = len(trace_columns), len(trace_columns[0]), len(coeffs)
+        num_challenges = len(challenges_by_point[0]) if challenges_by_point else 0
+        field = evaluators[0].field if evaluators else FIELD_FR
+        handles = (ctypes.c_uint64 * max(1, len(evaluators)))(*[ev.compiled(num_challenges, num_columns, lib) for ev in evaluators])
+        cols = GraphEvaluator._column_table([c for table in trace_columns for c in table])
+        flags = (ctypes.c_uint8 * max(1, num_columns))(*[1 if f else 0 for f in folded])
+        co = to_montgomery([v for row in coeffs for v in row], field)
+        ch = to_montgomery([v for row in challenges_by_point for v in row], field)
+        keep = (handles, cols, flags, co, ch)                # ctypes does not keep numpy arrays alive
+        return keep, (handles, len(evaluators), cols, num_columns, num_traces, flags, co.ctypes.data_as(ctypes.c_void_p),
+                      ch.ctypes.data_as(ctypes.c_void_p), num_challenges, num_points)
+
+    @staticmethod
+    def evaluate_folded_device(evaluators, trace_columns, folded, coeffs, challenges_by_point, num_rows, d_out, lib=None):
+        """mira_graph_eval_folded_device: every gate over every row of the folded trace sum_j coeffs[p][j] * trace_j, for every
+        evaluation point p at once -- FoldedTrace is never materialised.  The value of gate g at point p and `row` lands at
+        element (p * len(evaluators) + g) * num_rows + row of d_out; returns d_out."""
+        lib = lib or _lib.load()
+        keep, args = GraphEvaluator._folded_args(evaluators, trace_columns, folded, coeffs, challenges_by_point, lib)
+        lib.check(lib.c.mira_graph_eval_folded_device(*args, num_rows, ctypes.c_void_p(d_out)))
+        return d_out
+
+    @staticmethod
+    def evaluate_folded_reduce(evaluators, trace_columns, folded, coeffs, challenges_by_point, num_rows, weights, lib=None):
+        """mira_graph_eval_folded_reduce: the same evaluation reduced through compute_G's tree, node = left + right * weights[height],
+        without writing the leaves.  weights: ints, log2(len(evaluators) * num_rows) of them.  Returns the (points, 4) Montgomery
+        roots, the input of compute_G's small ifft."""
+        lib = lib or _lib.load()
+        keep, args = GraphEvaluator._folded_args(evaluators, trace_columns, folded, coeffs, challenges_by_point, lib)
+        field = evaluators[0].field if evaluators else FIELD_FR
+        w = to_montgomery(list(weights), field)
+        out = np.zeros((len(coeffs), 4), dtype=np.uint64)
+        lib.check(lib.c.mira_graph_eval_folded_reduce(*args, num_rows, w.ctypes.data_as(ctypes.c_void_p) if len(w) else None, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    @staticmethod
     def specialize(evaluators, columns, num_challenges, lib=None):
         """mira_graph_specialize: every one of these graphs gets a kernel of its own, compiled for the device at run
         time from its instruction stream (once per circuit: the gate polynomial is fixed for the whole IVC run).  Only
